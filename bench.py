@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the barcode-counting hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--reads R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--reads R] [--dump-outputs DIR]
 
 A *step* is one pass of the hot path (constant-flank scan -> variable-region extraction ->
 library match -> per-barcode count [-> RCCL all-reduce of the count vectors when N > 1]) over one
@@ -25,6 +25,9 @@ Rank 0 prints ONE JSON line: metric/value as BASELINE.json names them, plus
   e2e          -- (N = 1) PCIe-inclusive rates on bounded samples of the same stream, never `value`:
                   parsed batches in pinned host memory -> counts on the host (SURVEY.md 8d metric 1),
                   and FASTQ file (tmpfs) -> counts through the file-level C ABI entry point.
+
+--dump-outputs DIR writes the outputs of the last timed step as DIR/<name>.npy.  The read stream and the libraries are
+generated from fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -60,7 +63,12 @@ def parse_args():
     ap.add_argument("--cpu-cores", type=int, default=None, help="worker processes of the CPU baseline (default: this lease's CPU share)")
     ap.add_argument("--e2e-sample", type=int, default=None, help="reads in the pinned-batch end-to-end sample (0 disables)")
     ap.add_argument("--e2e-file-sample", type=int, default=None, help="reads in the FASTQ-file end-to-end sample (0 disables)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed, as its caller receives it, to DIR/<name>.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args) -> None:
@@ -222,6 +230,8 @@ def main() -> None:
     mapped = int(final_counts.sum())
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, plan, w.entry, np)
         unit = "Mpairs/s" if w.entry == "dual" else "Mreads/s"
         total_units = n * world * args.steps
         value = total_units / elapsed / 1e6
@@ -329,6 +339,28 @@ def main() -> None:
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, plan, entry, np) -> None:
+    """The arrays a caller of the timed path receives after its last step (the plan's counters still hold that step's counts,
+    all-reduced when N > 1): counts + total, or for combinations the sorted (indices, freq) runs + total.  Counts are
+    integers far below 2^53, so float64 holds them exactly."""
+    if entry == "combo":
+        idx, freq, total = plan.read_combo()
+        arrays = {"indices": idx, "freq": freq, "total": np.array([total])}
+    else:
+        counts, total = plan.read()
+        arrays = {"counts": counts, "total": np.array([total])}
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    size = sum(a.nbytes for a in arrays.values())
+    if size > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {size} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), a)
 
 
 def end_to_end(sc, synth, torch, np, w, plan, mates, args) -> dict:

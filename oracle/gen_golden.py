@@ -15,8 +15,11 @@ produced for them.  Two files:
         order-dependent cache and were run with nthreads=1.
   tests/golden/fastq_cases.json    -- FASTQ texts (incl. multi-line records, CRLF, missing final
         newline, malformed files) with the sequences / error kaori::FastqReader yields.
+  tests/golden/config_scale_kaori.json -- kaori's counts on the benchmark streams and libraries of configurations 2-5
+        (tests/test_gpu_config_parity.py) as digests with totals, sums and non-zero counts, and digests of the streams.
 
-    python oracle/gen_golden.py
+    python oracle/gen_golden.py            (everything)
+    python oracle/gen_golden.py configs    (only config_scale_kaori.json)
 """
 from __future__ import annotations
 
@@ -268,6 +271,48 @@ def config1_fixture(ref: KaoriRef, tmp: str) -> None:
     print(f"config 1: {int(counts.sum())} of {total} reads mapped")
 
 
+def config_scale_fixture(ref: KaoriRef, tmp: str) -> None:
+    """tests/golden/config_scale_kaori.json: real kaori's counts on the streams and libraries of BASELINE.json's configurations
+    2-5 at the sizes and option points of tests/test_gpu_config_parity.py, with a digest of each stream (the benchmark
+    generator's, synth.generate_host).  Per case: T.count_record of the counts (combinations as the dense n0 x n1 grid) --
+    a SHA-256 of the vector with its total, sum and non-zero entries, kept instead of the vectors for size -- and
+    reads_sha256.  One thread: the reference's search cache makes its dual path order-dependent with more
+    (SURVEY.md A.7), and its reduce() merges that cache while other workers read it."""
+    from screencounter_amd import synth
+    from tests import test_gpu_config_parity as T
+    cases = [(T.parity_key(c), c, n, None, None, False, None) for c, n in T.PARITY_READS.items()]
+    cases += [(T.option_key(*o), o[0], T.OPTION_READS, o[1], o[2], o[3], o[4]) for o in T.option_cases()]
+    out, streams = {}, {}
+    for key, config, n, use_first, strand, randomized, mismatches in cases:
+        w = synth.workload(config, n_reads=n)
+        if (config, n) not in streams:
+            host = [synth.generate_host(w, n, mate=m) for m in range(2 if w.entry == "dual" else 1)]
+            paths = []
+            for m, arr in enumerate(host):
+                paths.append(os.path.join(tmp, f"cfg{config}_{n}_{m}.fastq"))
+                synth.reads_to_fastq(paths[-1], arr, w.read_len)
+            streams[(config, n)] = (paths, T.stream_digest(host))
+            del host
+        paths, digest = streams[(config, n)]
+        use_first = w.use_first if use_first is None else use_first
+        strand = w.strand if strand is None else strand
+        if mismatches is not None:
+            w.mismatches = mismatches
+        if w.entry == "single":
+            counts, total = ref.count_single(paths[0], w.template, strand, w.pools[0], w.mismatches, use_first, 1)
+        elif w.entry == "combo":
+            idx, freq, total = ref.count_combo(paths[0], w.template, strand, w.pools[0], w.pools[1], w.mismatches, use_first, 1)
+            counts = T.dense_combo(idx, freq, len(w.pools[1]), len(w.pools[0]) * len(w.pools[1]))
+        else:
+            counts, total = ref.count_dual(paths[0], w.template, False, w.mismatches, w.pools[0], paths[1], w.template2, False,
+                                           w.mismatches, w.pools[1], randomized, use_first, 1)
+        out[key] = {**T.count_record(counts, total), "reads_sha256": digest}
+        print(f"{key}: {out[key]['mapped']} of {total} reads mapped", flush=True)
+    with open(os.path.join(OUT, "config_scale_kaori.json"), "w") as f:
+        json.dump({"generator": "oracle/gen_golden.py::config_scale_fixture", "reference": "kaori v1.1.1 (screenCounter 1.5.1)",
+                   "cases": out}, f, indent=1)
+
+
 def big_cases(ref: KaoriRef, tmp: str) -> None:
     """tests/golden/kaori_big.json: barcodes of 65..256 bases (as long as the longest template the reference compiles,
     src/count_single_barcodes.cpp:37-47) on every entry point; tests/golden/kaori_large_grid.json: countComboBarcodes with
@@ -316,7 +361,12 @@ def main() -> None:
         with tempfile.TemporaryDirectory() as tmp:
             big_cases(ref, tmp)
         return
+    if sys.argv[1:] == ["configs"]:                 # only tests/golden/config_scale_kaori.json
+        with tempfile.TemporaryDirectory() as tmp:
+            config_scale_fixture(ref, tmp)
+        return
     with tempfile.TemporaryDirectory() as tmp:
+        config_scale_fixture(ref, tmp)
         big_cases(ref, tmp)
         ka = [run_case(ref, c, tmp) for c in known_answers()]
         for c in ka:

@@ -70,3 +70,40 @@ def test_rccl_path_at_world_size_one(gpu):
         outs[forced] = json.loads(lines[0])
     assert "RCCL all-reduce" in outs["1"]["config"]["parallelism"] and "RCCL" not in outs["0"]["config"]["parallelism"]
     assert outs["1"]["mapped_fraction"] == outs["0"]["mapped_fraction"] and outs["1"]["n_gpus"] == 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("config", [2, 3])
+def test_dump_outputs(gpu, tmp_path, config):
+    """--dump-outputs DIR: what the last timed step computed, as float64 .npy files, identical from run to run and equal to
+    what a plan returns for the same seeded stream; --steps is the number of timed steps."""
+    import numpy as np
+    from screencounter_amd import synth
+    n = 2_000_000
+    args = ["--config", str(config), "--reads", str(n), "--steps", "3", "--warmup", "1", "--settle", "0", "--cpu-sample", "0",
+            "--e2e-sample", "0", "--e2e-file-sample", "0"]
+    names = ["counts", "total"] if config == 2 else ["indices", "freq", "total"]
+    dumps = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args + ["--dump-outputs", str(tmp_path / run)],
+                           env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["roofline"]["launches"] == 3 and out["ms_per_step"] > 0
+        assert sorted(f for f in os.listdir(tmp_path / run)) == sorted(f"{k}.npy" for k in names)
+        dumps.append({k: np.load(tmp_path / run / f"{k}.npy") for k in names})
+    for k in names:
+        assert dumps[0][k].dtype == np.float64
+        assert np.array_equal(dumps[0][k], dumps[1][k])
+    w = synth.workload(config, n_reads=n)
+    dw = synth.DeviceWorkload(w, gpu)
+    reads = dw.generate(n)
+    with dw.plan() as plan:
+        plan.count(reads, fixed_len=w.read_len, n_reads=n)
+        got = plan.read() if config == 2 else plan.read_combo()
+    want = dict(zip(names, got))
+    for k in names:
+        assert np.array_equal(dumps[0][k], np.asarray(want[k], dtype=np.float64).reshape(dumps[0][k].shape)), k
+    assert int(dumps[0]["total"][0]) == n

@@ -20,7 +20,7 @@ def driver(tmp_path_factory):
     cmd = [gxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include", "-D__HIP_PLATFORM_AMD__",
            os.path.join(ROOT, "tests", "ingest_asan_driver.cpp"), os.path.join(CSRC, "scg_ingest.cpp"), os.path.join(CSRC, "scg_fastq.cpp"),
-           "-lz", "-ldl", "-lpthread", "-o", exe]
+           os.path.join(CSRC, "scg_pgzip.cpp"), "-lz", "-ldl", "-lpthread", "-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         pytest.skip("host-only build of the ingestion code not possible here: " + r.stderr[-300:])
