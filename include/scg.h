@@ -320,6 +320,28 @@ int scg_plan_paired_combo(scg_plan** plan_out,
                           int randomized, int use_first,
                           int device, char* err, size_t errcap);
 
+/* Plan for countRandomBarcodes (kaori::RandomBarcodeSingleEnd, handlers/RandomBarcodeSingleEnd.hpp:86-181): the key of a
+ * read is its bytes in the FIRST forward variable region -- raw on the forward strand, reverse-complemented at the forward
+ * region's offset on the reverse strand -- as scg_count_random_barcodes counts them, tallied in HBM.  Counted with
+ * scg_count_batch (asynchronous, accumulates; the plan's calls run in call order whatever their streams), cleared by
+ * scg_plan_reset (capacity kept), read with scg_plan_read_random; scg_plan_num_counters is 0 and scg_plan_read gives the
+ * total.  Argument errors are those of scg_count_random_barcodes, raised before any device work.  The table starts at 2^16
+ * slots and doubles as needed; results never depend on its size.
+ * Test hook, read once here: SCG_TEST_RANDOM_TAG_BITS=b keeps b (0..61) hash bits in the tags of keys that are not pure
+ * upper-case ACGT of at most 31 bases, so that tests can make keys collide (counts stay exact) and exhaust the collision
+ * rounds (read-out then fails). */
+int scg_plan_random(scg_plan** plan_out, const char* constant, int strand, int mismatches, int use_first,
+                    int device, char* err, size_t errcap);
+
+/* Random-barcode plans: the tally of every batch counted since the last reset, in the layout scg_count_random_barcodes
+ * returns -- *sequences_out K NUL-terminated keys of *length_out characters (stride *length_out + 1) sorted byte-wise,
+ * *freq_out their K counts (release both with scg_free) -- and *total_out the reads counted.  Synchronises `stream`.
+ * Fails with the reference's "cannot complement unknown base 'X'" for the first read in counting order whose reverse
+ * region holds a byte other than ACGTN in either case (X: the rightmost such byte), when a read was longer than its
+ * batch's declared maximum, when a frequency exceeds INT32_MAX, or when keys collided in every hash round. */
+int scg_plan_read_random(scg_plan* plan, char** sequences_out, int32_t** freq_out, int64_t* k_out,
+                         int32_t* length_out, int64_t* total_out, void* stream, char* err, size_t errcap);
+
 void scg_plan_destroy(scg_plan* plan);
 
 /* Number of int32 counters the plan accumulates into: n_pool (single, dual) or

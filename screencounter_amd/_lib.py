@@ -104,6 +104,9 @@ SIGNATURES = {
                                         C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "scg_plan_read_diagnostics": (C.c_int, [C.c_void_p, i32_p, C.POINTER(i32_p), C.POINTER(i32_p), i64_p, i64_p, i32_p, i32_p,
                                             C.c_void_p, C.c_char_p, C.c_size_t]),
+    "scg_plan_random": (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    "scg_plan_read_random": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(i32_p), i64_p, i32_p, i64_p, C.c_void_p,
+                                       C.c_char_p, C.c_size_t]),
     "scg_plan_destroy": (None, [C.c_void_p]),
     "scg_plan_num_counters": (C.c_int64, [C.c_void_p]),
     "scg_plan_device_counters": (C.c_void_p, [C.c_void_p]),

@@ -245,6 +245,29 @@ int scg_plan_paired_combo(scg_plan** plan_out,
     });
 }
 
+int scg_plan_random(scg_plan** plan_out, const char* constant, int strand, int mismatches, int use_first,
+                    int device, char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (!plan_out) throw Error(SCG_ERR_INVALID, "null argument");
+        *plan_out = nullptr;
+        auto P = compile_random(constant, strand, mismatches, use_first);   // every argument check before any device work
+        P->to_device(device);
+        random_to_device(P.get());
+        *plan_out = P.release();
+    });
+}
+
+int scg_plan_read_random(scg_plan* plan, char** sequences_out, int32_t** freq_out, int64_t* k_out, int32_t* length_out, int64_t* total_out,
+                         void* stream, char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (!plan || !sequences_out || !freq_out || !k_out || !length_out) throw Error(SCG_ERR_INVALID, "null argument");
+        *sequences_out = nullptr; *freq_out = nullptr; *k_out = 0;
+        if (plan->kind != scg_plan::RANDOM) throw Error(SCG_ERR_INVALID, "not a random-barcode plan");
+        read_random(plan, static_cast<hipStream_t>(stream), sequences_out, freq_out, k_out, length_out);
+        if (total_out) *total_out = plan->total;
+    });
+}
+
 void scg_plan_destroy(scg_plan* plan) {
     if (!plan) return;
     int prev = -1;
@@ -260,6 +283,7 @@ int32_t* scg_plan_device_counters(scg_plan* plan) { return plan ? plan->counters
 int scg_plan_bind_counters(scg_plan* plan, int32_t* d_counters, char* err, size_t errcap) {
     return guarded(err, errcap, [&] {
         if (!plan) throw Error(SCG_ERR_INVALID, "null plan");
+        if (plan->kind == scg_plan::RANDOM) throw Error(SCG_ERR_INVALID, "random-barcode plans keep no counters to bind");
         plan->counters = d_counters ? d_counters : plan->own_counters.as<int32_t>();
     });
 }
@@ -268,6 +292,11 @@ int scg_plan_reset(scg_plan* plan, void* stream, char* err, size_t errcap) {
     return guarded(err, errcap, [&] {
         if (!plan) throw Error(SCG_ERR_INVALID, "null plan");
         DeviceGuard g(plan->device);
+        if (plan->kind == scg_plan::RANDOM) {                 // (ordered after the plan's previous call, like its batches)
+            random_reset(plan, static_cast<hipStream_t>(stream));
+            plan->total = 0;
+            return;
+        }
         HIP_CHECK(hipMemsetAsync(plan->counters, 0, static_cast<size_t>(plan->n_counters) * sizeof(int32_t), static_cast<hipStream_t>(stream)));
         HIP_CHECK(hipMemsetAsync(plan->error_flag.p, 0, sizeof(int32_t), static_cast<hipStream_t>(stream)));
         for (auto& kv : plan->pair_stream) {

@@ -184,8 +184,42 @@ using namespace scgapi;
 // -------------------------------------------------------------------------------------------------
 // Plans
 // -------------------------------------------------------------------------------------------------
+// countRandomBarcodes plans (scg_plan_random): the open-addressing tally in HBM (scg_random.hip).
+struct RandomTally {
+    DevBuf tags, counts, arena;     // capacity slots: uint64 tag, uint64 count, vlen key bytes (hashed tags only)
+    DevBuf state;                   // ScgRandomTable::state: first unknown-base error, occupied slots, unresolved reads
+    uint64_t cap = 0;
+    int32_t vstart = 0, vlen = 0, tag_bits = 61;
+    // growth bound: occupancy `known_occ` held after `known_at` reads; every read counted since may have added a key
+    int64_t known_occ = 0, known_at = 0;
+    PinnedBuf snap;                 // occupancy copied behind the batch that recorded snap_event
+    hipEvent_t snap_event = nullptr;
+    bool snap_pending = false;
+    int64_t snap_at = 0;
+    // batches of one plan run in call order, whichever streams they are on (the table may be reallocated between them)
+    hipEvent_t last = nullptr;
+    bool has_last = false;
+    struct Scratch { DevBuf hits, slots, list_a, list_b, lens; };
+    std::map<hipStream_t, Scratch> scratch;   // per stream, like scg_plan::unit_index
+
+    RandomTally() {}
+    RandomTally(const RandomTally&) = delete;
+    RandomTally& operator=(const RandomTally&) = delete;
+    ~RandomTally() {
+        if (snap_event) (void)hipEventDestroy(snap_event);
+        if (last) (void)hipEventDestroy(last);
+    }
+    scg::ScgRandomTable view() const {
+        scg::ScgRandomTable t;
+        t.tags = tags.as<unsigned long long>(); t.counts = counts.as<unsigned long long>(); t.arena = arena.as<uint8_t>();
+        t.state = state.as<unsigned long long>(); t.mask = cap - 1;
+        t.vstart = vstart; t.vlen = vlen; t.tag_bits = tag_bits; t.pad = 0;
+        return t;
+    }
+};
+
 struct scg_plan {
-    enum Kind { SINGLE, COMBO, DUAL, DUAL_SE_DIAG } kind = SINGLE;   // DUAL_SE_DIAG: single-end dual barcodes, include.invalid=TRUE
+    enum Kind { SINGLE, COMBO, DUAL, DUAL_SE_DIAG, RANDOM } kind = SINGLE;   // DUAL_SE_DIAG: single-end dual barcodes, include.invalid=TRUE
     int device = 0;
 
     // host-compiled pieces (valid before any device work)
@@ -227,6 +261,7 @@ struct scg_plan {
     std::map<hipStream_t, PairStream> pair_stream;
     std::unordered_map<uint64_t, int64_t> sparse_counts;
     int replica_shift = 0;   // log2(replicas)
+    std::unique_ptr<RandomTally> rnd;   // RANDOM plans
     DevBuf error_flag;   // set by a staged kernel that met a read longer than the declared maximum
     int32_t* counters = nullptr;
     int64_t n_counters = 0;
@@ -321,6 +356,10 @@ std::unique_ptr<scg_plan> compile_dual_single_end_diag(const char* constant, int
 std::unique_ptr<scg_plan> compile_paired_combo(const char* constant1, int reverse1, int mismatches1, const char* const* pool1, int32_t n1, const char* constant2,
                                                int reverse2, int mismatches2, const char* const* pool2, int32_t n2, int randomized, int use_first);
 void retire_all_pairs(scg_plan* P);
+std::unique_ptr<scg_plan> compile_random(const char* constant, int strand, int mismatches, int use_first);
+void random_to_device(scg_plan* P);
+void random_reset(scg_plan* P, hipStream_t stream);
+void read_random(scg_plan* P, hipStream_t stream, char** sequences_out, int32_t** freq_out, int64_t* k_out, int32_t* length_out);
 void launch_batch(scg_plan* P, const ScgReads& R, int64_t n, hipStream_t stream);
 void launch_batch_paired(scg_plan* P, const ScgReads& R1, const ScgReads& R2, int64_t n, hipStream_t stream);
 

@@ -27,6 +27,47 @@ hipError_t launch_tally(const int32_t* unit_index, int64_t n, int32_t* counters,
 size_t sort_rle_scratch_bytes(size_t n);
 hipError_t launch_sort_rle(const uint64_t* d_keys, uint64_t* d_sorted, size_t n, uint64_t* d_unique, uint32_t* d_counts, uint32_t* d_runs,
                            void* d_scratch, size_t scratch_bytes, hipStream_t stream);
+// ---- random-barcode plans: the tally in HBM (scg_random.hip) ----
+// Open-addressing table of capacity mask + 1 (a power of two).  Slot s: tags[s] (0 = empty), counts[s], and for hashed
+// tags the key bytes at arena[s * vlen].  Tag layout: bit 63 clear, bit 62 set, 2 bits per base MSB first below = a
+// packed key of pure upper-case ACGT of at most 31 bases; bit 63 set = a hashed key, bits 61-62 the round, the hash of
+// the bytes below (kept to tag_bits bits).  state[0]: the first unknown-base error, (read ordinal << 8) | byte, ~0 if
+// none; state[1]: occupied slots; state[2]: reads whose key collided in every round.
+#define SCG_RANDOM_ROUNDS 4
+struct ScgRandomTable {
+    unsigned long long* tags;
+    unsigned long long* counts;
+    uint8_t* arena;
+    unsigned long long* state;
+    uint64_t mask;
+    int32_t vstart, vlen;      // the first forward variable region (the key on both strands)
+    int32_t tag_bits;          // hash bits kept in a hashed tag (61; fewer only under the test hook)
+    int32_t pad;
+};
+// Round 0 of a batch: the key of every hit, aggregated per workgroup in LDS, claimed or found in the table;
+// slots[i] = its slot (bit 30 set for a hashed key; capacity <= 2^30) or -1.  ordinal0: counting-order number of read 0 (for the unknown-base error).
+hipError_t launch_random_insert(const ScgRandomTable& T, const ScgReads& R, int64_t n, const int32_t* hits, int32_t* slots,
+                                int64_t ordinal0, hipStream_t stream);
+// Round 0's verify: reads whose hashed key differs from its slot's arena bytes give back their count and join list_out
+// (lens[1] entries).  Then rounds 1 .. SCG_RANDOM_ROUNDS - 1 over the lists, lengths read on the device (lens[r]).
+// list_a, list_b: n entries each; lens: SCG_RANDOM_ROUNDS int32, zero on entry.
+hipError_t launch_random_verify_rounds(const ScgRandomTable& T, const ScgReads& R, int64_t n, const int32_t* hits, int32_t* slots,
+                                       int32_t* list_a, int32_t* list_b, int32_t* lens, hipStream_t stream);
+// Moves every entry of `from` into `to` (empty, larger); tags are capacity-independent and distinct.
+hipError_t launch_random_rehash(const ScgRandomTable& from, const ScgRandomTable& to, hipStream_t stream);
+// Read-out: occupied slots with a count -> packed (tag, count) and hashed (slot, count) lists; n_out[0] / n_out[1]
+// their lengths (zero on entry); each list has room for every occupied slot.
+hipError_t launch_random_compact(const ScgRandomTable& T, unsigned long long* packed_tags, unsigned long long* packed_counts,
+                                 int32_t* hashed_slots, unsigned long long* hashed_counts, unsigned long long* n_out, hipStream_t stream);
+size_t random_sort_scratch_bytes(size_t n);
+// Packed tags sorted with their counts on bits [0, end_bit): numeric order of packed tags is byte-wise order of the keys.
+hipError_t launch_random_sort(const unsigned long long* keys_in, unsigned long long* keys_out, const unsigned long long* vals_in,
+                              unsigned long long* vals_out, size_t n, int end_bit, void* scratch, size_t scratch_bytes, hipStream_t stream);
+// Packed tags -> n rows of vlen characters and a NUL (stride vlen + 1).
+hipError_t launch_random_decode(const unsigned long long* tags, int64_t n, int32_t vlen, char* out, hipStream_t stream);
+// Arena bytes of n slots -> n rows of vlen bytes.
+hipError_t launch_random_gather(const ScgRandomTable& T, const int32_t* slots, int64_t n, uint8_t* out, hipStream_t stream);
+
 hipError_t launch_match(const ScgIndex& tab, const uint8_t* d_seqs, int32_t n, int cap, int reverse,
                         int32_t* d_index, int32_t* d_mm, hipStream_t stream);
 hipError_t launch_synth(const scg_synth_spec& S, char* d_out, int64_t n, hipStream_t stream);

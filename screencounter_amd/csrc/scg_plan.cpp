@@ -422,7 +422,265 @@ void launch_batch_se_diag(scg_plan* P, const ScgReads& R, int64_t n, hipStream_t
     P->total += n;
 }
 
+// ---- countRandomBarcodes plans: the tally in HBM (scg_random.hip) ----
+
+// kaori::RandomBarcodeSingleEnd (handlers/RandomBarcodeSingleEnd.hpp:86-181) with the argument checks of the file entry
+// (scg_count_random_barcodes), in its order.  The key is the FIRST forward region on both strands, like the reference.
+std::unique_ptr<scg_plan> compile_random(const char* constant, int strand, int mismatches, int use_first) {
+    if (!constant) throw Error(SCG_ERR_INVALID, "null argument");
+    std::unique_ptr<scg_plan> P(new scg_plan);
+    P->kind = scg_plan::RANDOM;
+    P->ht1 = scg::parse_template(constant, strand);
+    const ScgTemplate& t = P->ht1.t;
+    if (t.nreg < 1) throw Error(SCG_ERR_INVALID, "expected one variable region in the constant template");
+    if (t.nreg > SCG_MAX_REGIONS) throw Error(SCG_ERR_UNSUPPORTED, "this engine handles templates with at most " + std::to_string(SCG_MAX_REGIONS) + " variable regions");
+    if (mismatches < 0) throw Error(SCG_ERR_INVALID, "negative number of mismatches");
+    P->scan1 = scg::build_scan(t, mismatches);
+    P->max_mm1 = mismatches;
+    P->use_first = use_first != 0;
+    P->n_counters = 0;
+    P->rnd.reset(new RandomTally);
+    P->rnd->vstart = t.fstart[0];
+    P->rnd->vlen = t.flen[0];
+    // Test hook, read here only: hashed tags keep this many hash bits (default and maximum 61), so that tests can make
+    // tags collide and exhaust the rounds.  Results never depend on it unless the rounds run out, which read-out reports.
+    if (const char* e = std::getenv("SCG_TEST_RANDOM_TAG_BITS")) {
+        if (*e) P->rnd->tag_bits = std::min(std::max(std::atoi(e), 0), 61);
+    }
+    return P;
+}
+
+namespace {
+
+const uint64_t RANDOM_INITIAL_SLOTS = uint64_t(1) << 16;
+const uint64_t RANDOM_MAX_SLOTS = uint64_t(1) << 30;     // slot indices travel in 30 bits (scg_random.hip)
+
+void swap_buf(DevBuf& a, DevBuf& b) { std::swap(a.p, b.p); std::swap(a.bytes, b.bytes); }
+
+void alloc_table(DevBuf& tags, DevBuf& counts, DevBuf& arena, uint64_t cap, int vlen) {
+    tags.alloc(cap * sizeof(unsigned long long));
+    counts.alloc(cap * sizeof(unsigned long long));
+    arena.alloc(cap * static_cast<uint64_t>(vlen));
+}
+
+// Every call on the plan waits for the previous one, on whichever stream that ran.
+void random_order(RandomTally& T, hipStream_t stream) {
+    if (T.has_last) HIP_CHECK(hipStreamWaitEvent(stream, T.last, 0));
+}
+void random_done(RandomTally& T, hipStream_t stream) {
+    HIP_CHECK(hipEventRecord(T.last, stream));
+    T.has_last = true;
+}
+
+ScgSingleParams random_params(const scg_plan* P) {
+    ScgSingleParams sp;
+    sp.scan = P->scan1;
+    sp.tmpl = P->d_tmpl1.as<ScgTemplate>();
+    std::memset(&sp.index, 0, sizeof(sp.index));
+    sp.max_mm = P->max_mm1; sp.use_first = P->use_first;
+    sp.fwd = P->ht1.fwd; sp.rev = P->ht1.rev;
+    return sp;
+}
+
+// Keeps occupancy <= capacity / 2 for the batch of n reads about to be counted on `stream`.  The bound is the last
+// occupancy known on the host plus every read counted since; only when it exceeds half the capacity is the exact
+// occupancy fetched (one synchronisation), and the table doubles while that plus n still does.
+void random_reserve(scg_plan* P, int64_t n, hipStream_t stream) {
+    RandomTally& T = *P->rnd;
+    if (T.snap_pending && hipEventQuery(T.snap_event) == hipSuccess) {
+        T.known_occ = static_cast<int64_t>(*T.snap.as<unsigned long long>());
+        T.known_at = T.snap_at;
+        T.snap_pending = false;
+    }
+    auto bound = [&] { return static_cast<uint64_t>(T.known_occ + (P->total - T.known_at) + n); };
+    if (bound() * 2 <= T.cap) return;
+    HIP_CHECK(hipMemcpyAsync(T.snap.p, T.state.as<unsigned long long>() + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    T.known_occ = static_cast<int64_t>(*T.snap.as<unsigned long long>());
+    T.known_at = P->total;
+    T.snap_pending = false;
+    uint64_t cap = T.cap;
+    while (bound() * 2 > cap) {
+        if (cap >= RANDOM_MAX_SLOTS) {
+            throw Error(SCG_ERR_UNSUPPORTED, "random barcode tally: " + std::to_string(bound()) + " possible keys exceed the table limit of " +
+                        std::to_string(RANDOM_MAX_SLOTS / 2) + " (read out, reset and count the rest in another plan)");
+        }
+        cap *= 2;
+    }
+    if (cap == T.cap) return;
+    DevBuf tags, counts, arena;
+    try {
+        alloc_table(tags, counts, arena, cap, T.vlen);
+    } catch (const Error& e) {
+        throw Error(SCG_ERR_DEVICE, "random barcode tally: cannot grow the table from " + std::to_string(T.cap) + " to " + std::to_string(cap) +
+                    " slots (" + e.what() + "); no key was dropped, the counts so far stay readable");
+    }
+    HIP_CHECK(hipMemsetAsync(tags.p, 0, tags.bytes, stream));
+    HIP_CHECK(hipMemsetAsync(counts.p, 0, counts.bytes, stream));
+    const scg::ScgRandomTable from = T.view();
+    scg::ScgRandomTable to = from;
+    to.tags = tags.as<unsigned long long>(); to.counts = counts.as<unsigned long long>(); to.arena = arena.as<uint8_t>(); to.mask = cap - 1;
+    HIP_CHECK(scg::launch_random_rehash(from, to, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));          // before the old table is released
+    swap_buf(T.tags, tags); swap_buf(T.counts, counts); swap_buf(T.arena, arena);
+    T.cap = cap;
+}
+
+void launch_batch_random(scg_plan* P, const ScgReads& R, int64_t n, hipStream_t stream) {
+    RandomTally& T = *P->rnd;
+    if (n >= INT32_MAX) throw Error(SCG_ERR_INVALID, "random-barcode plans take batches of fewer than 2^31 - 1 reads");
+    random_order(T, stream);
+    if (n > 0) {
+        random_reserve(P, n, stream);
+        RandomTally::Scratch& s = T.scratch[stream];
+        const size_t bytes = static_cast<size_t>(n) * sizeof(int32_t);
+        s.hits.ensure(bytes); s.slots.ensure(bytes); s.list_a.ensure(bytes); s.list_b.ensure(bytes);
+        s.lens.ensure(SCG_RANDOM_ROUNDS * sizeof(int32_t));
+        scg_plan::Timer timer(P, stream);
+        // a staged kernel that meets an oversize read flags it and leaves its hit unwritten: -1 there
+        HIP_CHECK(hipMemsetAsync(s.hits.p, 0xFF, bytes, stream));
+        HIP_CHECK(hipMemsetAsync(s.lens.p, 0, SCG_RANDOM_ROUNDS * sizeof(int32_t), stream));
+        HIP_CHECK(scg::launch_random(random_params(P), P->ht1.t.len, R, n, s.hits.as<int32_t>(), P->error_flag.as<int32_t>(), stream));
+        const scg::ScgRandomTable view = T.view();
+        HIP_CHECK(scg::launch_random_insert(view, R, n, s.hits.as<int32_t>(), s.slots.as<int32_t>(), P->total, stream));
+        HIP_CHECK(scg::launch_random_verify_rounds(view, R, n, s.hits.as<int32_t>(), s.slots.as<int32_t>(), s.list_a.as<int32_t>(),
+                                                   s.list_b.as<int32_t>(), s.lens.as<int32_t>(), stream));
+        timer.stop();
+        P->total += n;
+        if (!T.snap_pending) {
+            HIP_CHECK(hipMemcpyAsync(T.snap.p, T.state.as<unsigned long long>() + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipEventRecord(T.snap_event, stream));
+            T.snap_pending = true;
+            T.snap_at = P->total;
+        }
+    }
+    random_done(T, stream);
+}
+
+} // namespace
+
+void random_to_device(scg_plan* P) {
+    RandomTally& T = *P->rnd;
+    DeviceGuard g(P->device);
+    T.cap = RANDOM_INITIAL_SLOTS;
+    alloc_table(T.tags, T.counts, T.arena, T.cap, T.vlen);
+    T.state.alloc(4 * sizeof(unsigned long long));
+    T.snap.ensure(sizeof(unsigned long long));
+    HIP_CHECK(hipEventCreateWithFlags(&T.snap_event, hipEventDisableTiming));
+    HIP_CHECK(hipEventCreateWithFlags(&T.last, hipEventDisableTiming));
+    HIP_CHECK(hipMemset(T.tags.p, 0, T.tags.bytes));
+    HIP_CHECK(hipMemset(T.counts.p, 0, T.counts.bytes));
+    HIP_CHECK(hipMemset(T.state.p, 0, T.state.bytes));
+    HIP_CHECK(hipMemset(T.state.p, 0xFF, sizeof(unsigned long long)));   // no unknown-base error yet
+    HIP_CHECK(hipStreamSynchronize(nullptr));         // the fills are only enqueued (see scg_plan::to_device)
+}
+
+void random_reset(scg_plan* P, hipStream_t stream) {
+    RandomTally& T = *P->rnd;
+    random_order(T, stream);
+    HIP_CHECK(hipMemsetAsync(T.tags.p, 0, T.tags.bytes, stream));
+    HIP_CHECK(hipMemsetAsync(T.counts.p, 0, T.counts.bytes, stream));
+    HIP_CHECK(hipMemsetAsync(T.state.p, 0, T.state.bytes, stream));
+    HIP_CHECK(hipMemsetAsync(T.state.p, 0xFF, sizeof(unsigned long long), stream));
+    HIP_CHECK(hipMemsetAsync(P->error_flag.p, 0, sizeof(int32_t), stream));
+    random_done(T, stream);
+    T.known_occ = T.known_at = 0;
+    T.snap_pending = false;       // (a copy still in flight lands before any later one: the plan's calls are ordered)
+}
+
+// Read-out: occupied slots -> packed keys sorted on the device and decoded there, hashed keys' bytes sorted here; the two
+// sorted lists merged byte-wise (all keys have the same length).  Synchronises `stream`.
+void read_random(scg_plan* P, hipStream_t stream, char** sequences_out, int32_t** freq_out, int64_t* k_out, int32_t* length_out) {
+    RandomTally& T = *P->rnd;
+    DeviceGuard g(P->device);
+    random_order(T, stream);
+    unsigned long long st[4] = {0, 0, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(st, T.state.p, sizeof(st), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    if (st[0] != ~0ull) {                              // kaori/utils.hpp:117, first offending read in counting order
+        throw Error(SCG_ERR_INVALID, std::string("cannot complement unknown base '") + static_cast<char>(st[0] & 0xFF) + "'");
+    }
+    read_counters(P, nullptr);                         // reads longer than their batch's declared maximum
+    if (st[2]) {
+        throw Error(SCG_ERR_UNSUPPORTED, "random barcode tally: the keys of " + std::to_string(st[2]) + " reads collided with other keys in all " +
+                    std::to_string(SCG_RANDOM_ROUNDS) + " hash rounds; counts are incomplete");
+    }
+    const uint64_t occ = st[1];
+    const int vlen = T.vlen;
+    const size_t m = static_cast<size_t>(std::max<uint64_t>(occ, 1));
+    DevBuf ptags, pcounts, hslots, hcounts, nout;
+    ptags.alloc(m * 8); pcounts.alloc(m * 8); hslots.alloc(m * 4); hcounts.alloc(m * 8); nout.alloc(2 * 8);
+    HIP_CHECK(hipMemsetAsync(nout.p, 0, 2 * 8, stream));
+    HIP_CHECK(scg::launch_random_compact(T.view(), ptags.as<unsigned long long>(), pcounts.as<unsigned long long>(), hslots.as<int32_t>(),
+                                         hcounts.as<unsigned long long>(), nout.as<unsigned long long>(), stream));
+    unsigned long long nn[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(nn, nout.p, sizeof(nn), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    const size_t np = static_cast<size_t>(nn[0]), nh = static_cast<size_t>(nn[1]);
+    const size_t stride = static_cast<size_t>(vlen) + 1;
+    std::vector<unsigned long long> pc(np), hc(nh);
+    std::vector<char> pbytes(np * stride);
+    std::vector<uint8_t> hbytes(nh * static_cast<size_t>(vlen));
+    if (np) {
+        DevBuf stags, scounts, scratch, dec;
+        stags.alloc(np * 8); scounts.alloc(np * 8);
+        scratch.alloc(scg::random_sort_scratch_bytes(np));
+        dec.alloc(np * stride);
+        HIP_CHECK(scg::launch_random_sort(ptags.as<unsigned long long>(), stags.as<unsigned long long>(), pcounts.as<unsigned long long>(),
+                                          scounts.as<unsigned long long>(), np, 2 * vlen, scratch.p, scratch.bytes, stream));
+        HIP_CHECK(scg::launch_random_decode(stags.as<unsigned long long>(), static_cast<int64_t>(np), vlen, dec.as<char>(), stream));
+        HIP_CHECK(hipMemcpyAsync(pc.data(), scounts.p, np * 8, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(pbytes.data(), dec.p, np * stride, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
+    std::vector<size_t> horder(nh);
+    if (nh) {
+        DevBuf gathered;
+        gathered.alloc(hbytes.size());
+        HIP_CHECK(scg::launch_random_gather(T.view(), hslots.as<int32_t>(), static_cast<int64_t>(nh), gathered.as<uint8_t>(), stream));
+        HIP_CHECK(hipMemcpyAsync(hbytes.data(), gathered.p, hbytes.size(), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(hc.data(), hcounts.p, nh * 8, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        for (size_t i = 0; i < nh; ++i) horder[i] = i;
+        const uint8_t* hb = hbytes.data();
+        std::sort(horder.begin(), horder.end(), [&](size_t a, size_t b) {
+            return std::memcmp(hb + a * vlen, hb + b * vlen, static_cast<size_t>(vlen)) < 0;
+        });
+    }
+    random_done(T, stream);
+    auto narrow = [](unsigned long long c) {
+        if (c > static_cast<unsigned long long>(INT32_MAX)) {
+            throw Error(SCG_ERR_INVALID, "frequency of a random barcode (" + std::to_string(c) + ") exceeds the 32-bit range of the count vectors");
+        }
+        return static_cast<int32_t>(c);
+    };
+    const size_t K = np + nh;
+    char* so = static_cast<char*>(std::malloc(K * stride + 1));
+    int32_t* fo = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * (K + 1)));
+    if (!so || !fo) { std::free(so); std::free(fo); throw std::bad_alloc(); }
+    try {
+        size_t a = 0, b = 0;
+        for (size_t k = 0; k < K; ++k) {
+            const bool take_packed = b == nh ||
+                (a < np && std::memcmp(pbytes.data() + a * stride, hbytes.data() + horder[b] * vlen, static_cast<size_t>(vlen)) < 0);
+            if (take_packed) {
+                std::memcpy(so + k * stride, pbytes.data() + a * stride, stride);
+                fo[k] = narrow(pc[a++]);
+            } else {
+                std::memcpy(so + k * stride, hbytes.data() + horder[b] * vlen, static_cast<size_t>(vlen));
+                so[k * stride + vlen] = 0;
+                fo[k] = narrow(hc[horder[b++]]);
+            }
+        }
+    } catch (...) {
+        std::free(so); std::free(fo);
+        throw;
+    }
+    *sequences_out = so; *freq_out = fo; *k_out = static_cast<int64_t>(K); *length_out = vlen;
+}
+
 void launch_batch(scg_plan* P, const ScgReads& R, int64_t n, hipStream_t stream) {
+    if (P->kind == scg_plan::RANDOM) { launch_batch_random(P, R, n, stream); return; }
     if (P->kind == scg_plan::DUAL_SE_DIAG) { launch_batch_se_diag(P, R, n, stream); return; }
     scg_plan::Timer timer(P, stream);
     if (P->kind == scg_plan::SINGLE) {

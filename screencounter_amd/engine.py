@@ -137,6 +137,16 @@ class Plan:
                                       int(bool(randomized)), int(bool(use_first)), int(device), err, _lib.ERRCAP), err)
         return cls(h.value, "dual", (0,), device)
 
+    @classmethod
+    def random(cls, template: str, strand: int, mismatches: int = 0, use_first: bool = True, device: int = -1) -> "Plan":
+        """countRandomBarcodes: counted with count(), read with read_random().  The tally stays in HBM between batches."""
+        L = _lib.load()
+        h = C.c_void_p()
+        err = errbuf()
+        check(L.scg_plan_random(C.byref(h), template.encode(), int(strand), int(mismatches), int(bool(use_first)), int(device),
+                                err, _lib.ERRCAP), err)
+        return cls(h.value, "random", (0,), device)
+
     def close(self) -> None:
         if self._h:
             self._lib.scg_plan_destroy(self._h)
@@ -271,6 +281,26 @@ class Plan:
             self._lib.scg_free(idx_p)
             self._lib.scg_free(freq_p)
         return idx.astype(np.int32), freq.astype(np.int32), int(total.value)
+
+    def read_random(self, stream=None):
+        """Random-barcode plans: ((keys list[str] sorted byte-wise, freq int32[K]), total reads) of every batch counted
+        since the last reset -- the shape of api.count_random_barcodes."""
+        seq_p = C.c_void_p()
+        freq_p = _lib.i32_p()
+        k, vlen, total = C.c_int64(0), C.c_int32(0), C.c_int64(0)
+        err = errbuf()
+        rc = self._lib.scg_plan_read_random(self._h, C.byref(seq_p), C.byref(freq_p), C.byref(k), C.byref(vlen), C.byref(total),
+                                            C.c_void_p(_stream_handle(stream)), err, _lib.ERRCAP)
+        try:
+            check(rc, err)
+            K, W = int(k.value), int(vlen.value)
+            blob = C.string_at(seq_p, K * (W + 1)) if K else b""
+            seqs = [blob[i * (W + 1): i * (W + 1) + W].decode("latin-1") for i in range(K)]
+            freq = np.ctypeslib.as_array(freq_p, shape=(max(K, 1),))[:K].copy().astype(np.int32) if K else np.zeros(0, dtype=np.int32)
+        finally:
+            self._lib.scg_free(seq_p)
+            self._lib.scg_free(freq_p)
+        return (seqs, freq), int(total.value)
 
     # ---- measurement ----------------------------------------------------------------------------
     def set_profiling(self, enabled: bool) -> None:
