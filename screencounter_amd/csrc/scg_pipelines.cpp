@@ -49,10 +49,8 @@ void count_single_end_file(scg_plan* P, const char* path, scg::FastqStream& fq, 
         }
         st.drain();
         if (!pf.unusual()) return;
-        // start over with the reference-exact sequential reader
-        if (P->n_counters) HIP_CHECK(hipMemset(P->counters, 0, static_cast<size_t>(P->n_counters) * sizeof(int32_t)));
-        HIP_CHECK(hipStreamSynchronize(nullptr));           // (the fill is only enqueued: scg_plan::upload)
-        P->total = 0;
+        // start over with the reference-exact sequential reader; what the windows counted goes, sparse combinations included
+        reset_plan(P);
         if (restart) restart();
     }
     scg::ReadBatch b;
@@ -1411,9 +1409,7 @@ void count_paired_host(scg_plan* P, const char* path1, const char* path2, scg::F
             }
             return;
         }
-        HIP_CHECK(hipMemset(P->counters, 0, static_cast<size_t>(P->n_counters) * sizeof(int32_t)));
-        HIP_CHECK(hipStreamSynchronize(nullptr));
-        P->total = 0;
+        reset_plan(P);                  // (as above: the windows' counts go, dense and sparse)
     }
     scg::ReadBatch b1, b2;
     for (;;) {

@@ -358,3 +358,41 @@ def fastq_text(reads, name_prefix: str = "r", trailing_newline: bool = True) -> 
     out = b"".join(b"@%s%d some comment\n" % (name_prefix.encode(), i) + (r.encode() if isinstance(r, str) else bytes(r)) + b"\n+\n" +
                    b"I" * len(r) + b"\n" for i, r in enumerate(reads))
     return out if trailing_newline else out[:-1]
+
+
+def fastq_record(i: int, read, flaw: str = None, name_prefix: str = "r", rng: random.Random = None) -> bytes:
+    """One FASTQ record as `fastq_text` writes it, or one of the forms only the sequential reader accepts or reports:
+
+    * "multiline": sequence and quality each split over two lines (legal, FastqReader.hpp:66-84);
+    * "oversized": the read padded with random bases to ~16 KB, longer than the parallel reader's window under a small
+      $SCG_FASTQ_PIECE_KB (legal);
+    * "malformed": a quality string one byte shorter than the sequence (illegal: the reference's error)."""
+    s = read.encode() if isinstance(read, str) else bytes(read)
+    head = b"@%s%d some comment\n" % (name_prefix.encode(), i)
+    if flaw is None:
+        return head + s + b"\n+\n" + b"I" * len(s) + b"\n"
+    if flaw == "multiline":
+        if len(s) < 2:
+            raise ValueError("a multi-line record needs a read of at least 2 bases")
+        h = len(s) // 2
+        return head + s[:h] + b"\n" + s[h:] + b"\n+\n" + b"I" * h + b"\n" + b"I" * (len(s) - h) + b"\n"
+    if flaw == "oversized":
+        s += rand_seq(rng or random.Random(i), 16 * 1024).encode()
+        return head + s + b"\n+\n" + b"I" * len(s) + b"\n"
+    if flaw == "malformed":
+        s = s or b"A"
+        return head + s + b"\n+\n" + b"I" * (len(s) - 1) + b"\n"
+    raise ValueError(f"unknown flaw {flaw!r}")
+
+
+def write_flawed_fastq(path, reads, flaws: dict = None, seed: int = 0) -> str:
+    """A FASTQ file of strict 4-line records except at the record indices of `flaws` ({index: kind}, kinds as in
+    `fastq_record`).  For a paired run, call it once per mate with each mate's own flaws.  The expected result is always
+    taken from parsing the written file with the oracle, never from `reads` (a multi-line or oversized record changes
+    neither the read nor the count of reads, but a flaw the reference rejects ends the parse)."""
+    rng = random.Random(seed)
+    flaws = flaws or {}
+    with open(path, "wb") as f:
+        for i, r in enumerate(reads):
+            f.write(fastq_record(i, r, flaws.get(i), rng=rng))
+    return str(path)
