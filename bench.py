@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the barcode-counting hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--reads R] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--reads R] [--dump-outputs DIR] [--full]
 
 A *step* is one pass of the hot path (constant-flank scan -> variable-region extraction ->
 library match -> per-barcode count [-> RCCL all-reduce of the count vectors when N > 1]) over one
@@ -18,13 +18,17 @@ reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment as usual.
 
 Rank 0 prints ONE JSON line: metric/value as BASELINE.json names them, plus
   roofline     -- algorithmic bytes (sum of read lengths) / average counting-kernel duration
-                  measured with HIP events on the launch stream, against the 8 TB/s HBM peak
+                  measured with HIP events on the launch stream during the timed steps, against the 8 TB/s HBM peak
+A plain run stops there: it sets up, warms up, times the steps, writes --dump-outputs and prints the line.
+--full then measures more on the same process and stream, after the timed steps (these keys are null or absent
+without it):
   cpu_baseline -- the reference CPU path (real kaori via oracle/_ref when present) timed on this
                   box's host cores on a bounded prefix of the same stream, N = 1 only, with the
                   GPU counts on that prefix checked bit-exact against it
   e2e          -- (N = 1) PCIe-inclusive rates on bounded samples of the same stream, never `value`:
                   parsed batches in pinned host memory -> counts on the host (SURVEY.md 8d metric 1),
                   and FASTQ file (tmpfs) -> counts through the file-level C ABI entry point.
+  vs_cpu_reference -- `value` and every e2e leg over cpu_baseline.value.
 
 --dump-outputs DIR writes the outputs of the last timed step as DIR/<name>.npy.  The read stream and the libraries are
 generated from fixed seeds, so two builds run with the same arguments can be compared output for output.
@@ -59,10 +63,12 @@ def parse_args():
     ap.add_argument("--config", type=int, default=2, help="BASELINE.json config: 2 single (default), 3 combo, 4 dual, 5 single <=2mm")
     ap.add_argument("--reads", type=int, default=None, help="reads (pairs) per GPU; default = the config's full size")
     ap.add_argument("--library", type=int, default=None, help="override the library size (tests only)")
-    ap.add_argument("--cpu-sample", type=int, default=None, help="reads in the CPU-baseline sample (0 disables)")
-    ap.add_argument("--cpu-cores", type=int, default=None, help="worker processes of the CPU baseline (default: this lease's CPU share)")
-    ap.add_argument("--e2e-sample", type=int, default=None, help="reads in the pinned-batch end-to-end sample (0 disables)")
-    ap.add_argument("--e2e-file-sample", type=int, default=None, help="reads in the FASTQ-file end-to-end sample (0 disables)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the CPU baseline (with its parity check) and the PCIe-inclusive e2e legs")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="(--full) reads in the CPU-baseline sample (0 disables)")
+    ap.add_argument("--cpu-cores", type=int, default=None, help="(--full) worker processes of the CPU baseline (default: this host's CPU share)")
+    ap.add_argument("--e2e-sample", type=int, default=None, help="(--full) reads in the pinned-batch end-to-end sample (0 disables)")
+    ap.add_argument("--e2e-file-sample", type=int, default=None, help="(--full) reads in the FASTQ-file end-to-end sample (0 disables)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed, as its caller receives it, to DIR/<name>.npy (float64)")
     args = ap.parse_args()
@@ -242,6 +248,7 @@ def main() -> None:
         # separate rocprofv3 --pmc runs of this same command, gfx950 correction applied: DESIGN.md section 5)
         # (counting kernel + the tally kernel that turns its index stream into counts)
         traffic, traffic_source, rocprof_ms, rocprof_source = None, None, None, None
+        full_size = args.reads is None or n == synth.workload(args.config).n_reads
         try:
             with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
                 rec = json.load(f).get(str(args.config))
@@ -274,9 +281,9 @@ def main() -> None:
                          "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
                          "kernel": KERNEL_OF[w.entry], "avg_kernel_ms": round(avg_kernel_s * 1e3, 4), "launches": launches,
                          # the committed rocprofv3 summary of this command (full-size runs only), next to the live HIP-event figure
-                         "rocprof_avg_kernel_ms": rocprof_ms if n == synth.workload(args.config).n_reads else None,
+                         "rocprof_avg_kernel_ms": rocprof_ms if full_size else None,
                          "rocprof_frac": (round(algo_bytes / (rocprof_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 5)
-                                          if rocprof_ms and n == synth.workload(args.config).n_reads else None),
+                                          if rocprof_ms and full_size else None),
                          "rocprof_source": rocprof_source,
                          "algorithmic_bytes_per_launch": algo_bytes, "traffic_source": traffic_source,
                          # the whole step (counting kernel + tally / fold kernel [+ all-reduce]) against the same peak
@@ -288,7 +295,7 @@ def main() -> None:
         sample = args.cpu_sample
         if sample is None:
             sample = min(n, 50_000_000 if w.entry != "dual" else 20_000_000)
-        if world == 1 and sample > 0:
+        if args.full and world == 1 and sample > 0:
             from oracle import cpu_baseline
             sample = min(sample, n)
             cores, visible, why = cpu_share()
@@ -318,7 +325,7 @@ def main() -> None:
             out["cpu_baseline"] = None
 
         out["e2e"] = None
-        if world == 1:
+        if args.full and world == 1:
             try:
                 out["e2e"] = end_to_end(sc, synth, torch, np, w, plan, mates, args)
             except Exception as e:      # the PCIe legs are informative; the headline line must still print

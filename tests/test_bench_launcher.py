@@ -38,7 +38,7 @@ def test_parent_does_not_import_torch_before_launching():
 def test_two_ranks_on_one_gpu_rehearsal(gpu):
     """N = 2 ranks sharing the one GPU of this box (gloo for the count reduce): rc 0, one JSON line, whole-job
     value = 2 shards, and the reduced counts are the sum of two different shards (mapped fraction as at N = 1)."""
-    args = ["--config", "2", "--reads", "3000000", "--steps", "3", "--warmup", "1", "--settle", "0", "--cpu-sample", "0"]
+    args = ["--config", "2", "--reads", "3000000", "--steps", "3", "--warmup", "1", "--settle", "0", "--cpu-sample", "0", "--full"]
     outs = {}
     for n in (1, 2):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)] + args,
@@ -70,6 +70,21 @@ def test_rccl_path_at_world_size_one(gpu):
         outs[forced] = json.loads(lines[0])
     assert "RCCL all-reduce" in outs["1"]["config"]["parallelism"] and "RCCL" not in outs["0"]["config"]["parallelism"]
     assert outs["1"]["mapped_fraction"] == outs["0"]["mapped_fraction"] and outs["1"]["n_gpus"] == 1
+
+
+@pytest.mark.gpu
+def test_plain_run_measures_only_the_steps(gpu):
+    """Without --full the bench runs neither the CPU baseline nor the e2e legs, even with their sample sizes left at the
+    defaults: the line holds the timed steps and their roofline."""
+    args = ["--config", "2", "--reads", "2000000", "--steps", "3", "--warmup", "1", "--settle", "0"]
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args,
+                       env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["cpu_baseline"] is None and out["e2e"] is None and "vs_cpu_reference" not in out
+    assert out["steps"] == 3 and out["roofline"]["launches"] == 3 and out["value"] > 0 and out["mapped_fraction"] > 0
 
 
 @pytest.mark.gpu

@@ -1,7 +1,7 @@
 """BASELINE.json's full sizes, checked through properties that do not need an oracle run of that size:
 additivity over shards of the read stream, agreement of the two independent counting paths (memory-side
 atomics vs index stream + LDS tally), agreement of the two engines on a slice of the same stream, and
-reset idempotence.  (The bench re-checks a 50 M-read prefix against real kaori in the same run.)"""
+reset idempotence.  (`bench.py --full` re-checks a 50 M-read prefix against real kaori in the same run.)"""
 import numpy as np
 import pytest
 

@@ -5,6 +5,7 @@
 # (with the CPU baseline and its parity check).
 # usage: tools/make_profiles.sh <tag> [config]
 TAG=$1; CFG=${2:-2}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/profiles_${TAG}_config$CFG
 mkdir -p $OUT
 B="$GRAFT_REPO_ROOT/bench.py --config $CFG --cpu-sample 0 --e2e-sample 0 --e2e-file-sample 0 --settle 0"
@@ -33,4 +34,4 @@ for P in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_
 done
 KSUB=staged; [ "$CFG" = "4" ] && KSUB=dual_passes      # (the pair search in two passes: dual_passes_kernel)
 python3 $GRAFT_REPO_ROOT/tools/pmc_summary.py $OUT/sq $KSUB > $OUT/pmc_summary.txt 2>&1
-cd $GRAFT_REPO_ROOT && timeout -k 10 900 python bench.py --config $CFG > $OUT/bench_default.log 2>&1; echo "bench rc=$?"; tail -1 $OUT/bench_default.log | cut -c1-400
+cd "$ROOT" && timeout -k 10 900 python bench.py --config $CFG --full > $OUT/bench_default.log 2>&1; echo "bench rc=$?"; tail -1 $OUT/bench_default.log | cut -c1-400
