@@ -396,3 +396,92 @@ def write_flawed_fastq(path, reads, flaws: dict = None, seed: int = 0) -> str:
         for i, r in enumerate(reads):
             f.write(fastq_record(i, r, flaws.get(i), rng=rng))
     return str(path)
+
+
+# ---------------------------------------------------------------------------------------------
+# Constructed inputs for the staged kernels' tile and dispatch boundaries (tests/test_gpu_tile_edges.py).
+# ---------------------------------------------------------------------------------------------
+def segments_template(rng: random.Random, segments) -> str:
+    """[("c", n) | ("v", n), ...] -> template: n random constant bases or n '-' per segment."""
+    return "".join(rand_seq(rng, n) if kind == "c" else "-" * n for kind, n in segments)
+
+
+def seed_blocks(positions, max_mm: int, seed_max: int = 9, max_seeds: int = 4) -> list[int]:
+    """Blocks (of 32 template positions) of the pigeonhole seeds the host chooses for the constant positions of one strand
+    (mirror of build_scan in scg_library.cpp): runs of up to seed_max consecutive constant positions inside one block,
+    the longest first, earlier ones first among equals; runs are split when there are fewer than max_mm + 1."""
+    want = max_mm + 1
+    if want > max_seeds or len(positions) < want:
+        return []
+    runs = []
+    k = 0
+    while k < len(positions):
+        blk = positions[k] >> 5
+        n = 1
+        while k + n < len(positions) and n < seed_max and positions[k + n] >> 5 == blk:
+            n += 1
+        runs.append([k, n, blk])
+        k += n
+    while len(runs) < want:
+        big = max(range(len(runs)), key=lambda i: (runs[i][1], -i))
+        first, n, blk = runs[big]
+        if n < 2:
+            break
+        runs[big:big + 1] = [[first, n // 2, blk], [first + n // 2, n - n // 2, blk]]
+    if len(runs) < want:
+        return []
+    chosen = sorted(runs, key=lambda r: -r[1])[:want]       # stable: earlier runs first among equals
+    return [r[2] for r in chosen]
+
+
+def compact_ok(template: str, max_mm: int) -> bool:
+    """Whether the host allows the compact candidate form (NC = 3) for this template: every seed of both strands lies in
+    template block 0 or 1."""
+    L = len(template)
+    fpos = [i for i, c in enumerate(template) if c != "-"]
+    rpos = sorted(L - 1 - i for i in fpos)
+    return all(b <= 1 for b in seed_blocks(fpos, max_mm) + seed_blocks(rpos, max_mm))
+
+
+def chance_hits(template: str, max_mm: int, read_len: int) -> float:
+    """expected_chance_hits of scg_kernels.hip: windows of a random read that pass the template's constant bases."""
+    c = sum(ch != "-" for ch in template)
+    ways, choose, pow3 = 0.0, 1.0, 1.0
+    for k in range(min(max_mm, c) + 1):
+        ways += choose * pow3
+        choose = choose * (c - k) / (k + 1)
+        pow3 *= 3
+    return (read_len - len(template) + 1 if read_len > len(template) else 1) * ways / 4.0 ** c
+
+
+class Filler:
+    """Fast random ACGT padding: slices of one long random string."""
+
+    def __init__(self, seed: int, size: int = 1 << 16):
+        self.rng = random.Random(seed)
+        self.text = rand_seq(self.rng, size)
+
+    def __call__(self, n: int) -> str:
+        if n <= 0:
+            return ""
+        a = self.rng.randrange(0, len(self.text) - n)
+        return self.text[a:a + n]
+
+
+def place(fill: Filler, construct: str, n: int, pos: int) -> str:
+    """A read of n bases holding `construct` at position pos, random bases around it."""
+    assert 0 <= pos and pos + len(construct) <= n, (pos, len(construct), n)
+    return fill(pos) + construct + fill(n - pos - len(construct))
+
+
+def substitute(s: str, i: int, c: str = None) -> str:
+    """s with base i replaced by c (default: a different base)."""
+    if c is None:
+        c = "A" if s[i].upper() != "A" else "C"
+    return s[:i] + c + s[i + 1:]
+
+
+def split_pair(fill: Filler, construct: str, k: int, n1: int, n2: int) -> tuple[str, str]:
+    """Two neighbouring reads: the first (n1 bases) ends with the construct's first k bases, the second (n2 bases)
+    starts with the rest."""
+    return fill(n1 - k) + construct[:k], construct[k:] + fill(n2 - (len(construct) - k))
