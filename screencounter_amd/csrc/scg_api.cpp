@@ -1,5 +1,5 @@
-// scg_api.cpp -- the C ABI (include/scg.h): every entry point, over the plans (scg_plan.cpp) and the pipelines
-// (scg_pipelines.cpp).
+// scg_api.cpp -- the C ABI (include/scg.h): every entry point, over the plans (scg_plan.cpp) and the file
+// entries (scg_files.cpp, scg_results.cpp).
 //
 // Host-side counterpart of the reference's Rcpp glue (src/count_single_barcodes.cpp,
 // src/count_combo_barcodes_single.cpp, src/count_dual_barcodes.cpp, src/match_barcodes.cpp): same argument order,

@@ -1,6 +1,7 @@
-// scg_internal.hpp -- what the three parts of the host side share: error plumbing, device buffers, the plan object, and the
-// functions one part calls in another.  scg_plan.cpp: plan compilation and batch launches; scg_pipelines.cpp: FASTQ files
-// to counts (staging, windows, devices); scg_api.cpp: the C entry points of include/scg.h.
+// scg_internal.hpp -- what the parts of the host side share: error plumbing, device buffers, the plan object, and the
+// functions one part calls in another.  scg_plan.cpp: plan compilation and batch launches; scg_files.cpp: FASTQ files to
+// counts (the fall-back ladders and file entries, over the windows of scg_windows.hpp); scg_results.cpp: devices, plan
+// sets and result shaping; scg_api.cpp: the C entry points of include/scg.h.
 #ifndef SCG_INTERNAL_HPP
 #define SCG_INTERNAL_HPP
 #include <hip/hip_runtime_api.h>
@@ -114,6 +115,14 @@ struct DeviceGuard {
         if (prev != device) HIP_CHECK(hipSetDevice(device)); else prev = -1;
     }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+// The same for destructors: never throws, and a device that cannot be made current is left alone.
+struct QuietDeviceGuard {
+    int prev = -1;
+    explicit QuietDeviceGuard(int device) noexcept {
+        if (device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != device) (void)hipSetDevice(device); else prev = -1;
+    }
+    ~QuietDeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
 struct DevBuf {
@@ -363,7 +372,7 @@ void read_random(scg_plan* P, hipStream_t stream, char** sequences_out, int32_t*
 void launch_batch(scg_plan* P, const ScgReads& R, int64_t n, hipStream_t stream);
 void launch_batch_paired(scg_plan* P, const ScgReads& R1, const ScgReads& R2, int64_t n, hipStream_t stream);
 
-// ---- scg_pipelines.cpp ----
+// ---- scg_files.cpp ----
 // ---- FASTQ -> device staging: two slots, each with its own stream, pinned and device buffers ----
 struct Stager {
     static const int SLOTS = 2;
@@ -446,28 +455,53 @@ struct PlanSet {
     std::unordered_map<uint64_t, int64_t> sparse_merged() const;
 };
 
+// The switches that steer the file paths (test hooks and tuning aids), read once per file-level call.
+struct Switches {
+    bool device_scan = true;      // SCG_DEVICE_SCAN=0 keeps the host parsers
+    bool host_scan = true;        // SCG_HOST_SCAN=0 ships the raw text of plain files too
+    bool buffer_cache = true;     // SCG_BUFFER_CACHE=0 keeps no idle scan slots for the next call
+    bool device_inflate = true;   // SCG_DEVICE_INFLATE=0 inflates BGZF members on the host threads
+    // =2: a file the device inflater / gzip decoder hands back is an error instead of a quiet second try on the host
+    // (so that a test on a well-formed file cannot pass on the fall-back)
+    bool inflate_strict = false, gunzip_strict = false;      // SCG_DEVICE_INFLATE=2, SCG_DEVICE_GUNZIP=2
+    size_t window_kb = 0;         // SCG_WINDOW_KB: tiny windows force many hand-overs (0: the built-in sizes)
+    Switches() {
+        auto first = [](const char* name) { const char* e = std::getenv(name); return e ? *e : '\0'; };
+        device_scan = first("SCG_DEVICE_SCAN") != '0';
+        host_scan = first("SCG_HOST_SCAN") != '0';
+        buffer_cache = first("SCG_BUFFER_CACHE") != '0';
+        device_inflate = first("SCG_DEVICE_INFLATE") != '0';
+        inflate_strict = first("SCG_DEVICE_INFLATE") == '2';
+        gunzip_strict = first("SCG_DEVICE_GUNZIP") == '2';
+        if (const char* e = std::getenv("SCG_WINDOW_KB")) window_kb = static_cast<size_t>(std::max(0L, std::atol(e)));
+    }
+};
+
 void count_single_end_file(scg_plan* P, const char* path, scg::FastqStream& fq, int nthreads,
                            const std::function<void(Stager::Slot&, const ScgReads&, int64_t)>& launch = nullptr,
                            const std::function<void(Stager::Slot&)>& retire = nullptr,
                            const std::function<void()>& restart = nullptr);
 void release_cached_slots();
-void reset_plan(scg_plan* P);
 bool is_parallel_gzip(const scg::TextSource* s);
 void count_single_end(const std::vector<scg_plan*>& plans, const char* path, scg::FastqStream& fq, int nthreads);
+void count_paired_files(scg_plan* P, const char* path1, const char* path2, scg::FastqStream& fq1, scg::FastqStream& fq2, int nthreads);
+std::unique_ptr<PlanSet> compile_and_count_single_end(const char* path, scg::FastqStream& fq, int nthreads, Compile compile);
+std::unique_ptr<PlanSet> compile_and_count_paired(const char* path1, const char* path2, scg::FastqStream& fq1, scg::FastqStream& fq2, int nthreads, Compile compile);
+
+// ---- scg_results.cpp ----
+void reset_plan(scg_plan* P);
 int32_t narrow_total(int64_t total);
 void read_counters(scg_plan* P, int32_t* counts_out);
 std::vector<int> device_list(bool* explicit_list = nullptr);
+std::vector<int> devices_for_input(uint64_t text_bytes, size_t window);
+uint64_t text_bytes_hint(const char* path);
 void set_thread_devices(const int* devices, int32_t n);      // scg_set_devices()
 std::unique_ptr<scg_plan> clone_compiled(const scg_plan& a);
 void schedule_files(int32_t n_files, const PlanSet& set, const std::function<void(scg_plan*, int32_t)>& per_file);
-std::unique_ptr<PlanSet> compile_and_count_single_end(const char* path, scg::FastqStream& fq, int nthreads, Compile compile);
 void combo_compact(const int32_t* cells, int32_t n0, int32_t n1, int32_t** indices_out, int32_t** freq_out, int64_t* k_out);
 void combos_from_sparse(const std::unordered_map<uint64_t, int64_t>& m, int32_t** indices_out, int32_t** freq_out, int64_t* k_out);
 void diagnostics_from_counters(const scg_plan* P, const std::vector<int32_t>& all, int32_t* counts_out, int32_t** idx_out, int32_t** freq_out, int64_t* k_out,
                                int32_t* b1, int32_t* b2, const std::unordered_map<uint64_t, int64_t>* sparse = nullptr);
-void count_paired_files(scg_plan* P, const char* path1, const char* path2, scg::FastqStream& fq1, scg::FastqStream& fq2, int nthreads,
-                        bool try_device_inflate = true, bool parallel_gzip = true);
-std::unique_ptr<PlanSet> compile_and_count_paired(const char* path1, const char* path2, scg::FastqStream& fq1, scg::FastqStream& fq2, int nthreads, Compile compile);
 
 } // namespace scgapi
 

@@ -1,0 +1,290 @@
+// scg_results.cpp -- what a file-level call has around its pipelines: the devices it may use, the plans on them (PlanSet),
+// the scheduling of many files over them, and the shaping of counters into the reference's outputs.
+#include "scg_internal.hpp"
+
+namespace scgapi {
+
+void reset_plan(scg_plan* P) {
+    DeviceGuard g(P->device);
+    if (P->n_counters) HIP_CHECK(hipMemset(P->counters, 0, static_cast<size_t>(P->n_counters) * sizeof(int32_t)));
+    if (P->replica_shift > 0) HIP_CHECK(hipMemset(P->replicas.p, 0, P->replicas.bytes));
+    HIP_CHECK(hipStreamSynchronize(nullptr));               // (the fills are only enqueued: scg_plan::upload)
+    for (auto& kv : P->pair_stream) {                       // (sparse mode: batches in flight are let finish and dropped)
+        if (kv.second.pending) { HIP_CHECK(hipEventSynchronize(kv.second.done)); kv.second.pending = 0; }
+    }
+    P->sparse_counts.clear();
+    P->total = 0;
+}
+
+// The reference's totals and counters are 32-bit `int`s (SingleBarcodeSingleEnd.hpp:132-133) and R integers
+// are 32-bit; a file with more reads than that would overflow them silently there.  Here the total is kept
+// in 64 bits and narrowing at the ABI is checked; no counter can exceed the total.
+int32_t narrow_total(int64_t total) {
+    if (total > static_cast<int64_t>(INT32_MAX)) {
+        throw Error(SCG_ERR_INVALID, "number of reads (" + std::to_string(total) + ") exceeds the 32-bit range of the count vectors");
+    }
+    return static_cast<int32_t>(total);
+}
+
+void read_counters(scg_plan* P, int32_t* counts_out) {
+    int32_t flag = 0;
+    HIP_CHECK(hipMemcpy(&flag, P->error_flag.p, sizeof(flag), hipMemcpyDeviceToHost));
+    if (flag) {
+        throw Error(SCG_ERR_INVALID, "a read is longer than the max_len declared for its batch: counts are incomplete");
+    }
+    if (counts_out && P->n_counters) {
+        HIP_CHECK(hipMemcpy(counts_out, P->counters, static_cast<size_t>(P->n_counters) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+}
+
+// ---- devices and plan sets ---------------------------------------------------------------------------------
+// Which devices a file-level call may use: $SCG_DEVICES ("all", or a comma list in which an id may repeat: several
+// pipelines on one card) if set; else every visible device, the calling thread's current one ($SCG_DEVICE) first.
+thread_local std::vector<int> tl_devices;       // scg_set_devices(): overrides $SCG_DEVICES for the calling thread
+
+std::vector<int> device_list(bool* explicit_list) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+        throw Error(SCG_ERR_DEVICE, "no HIP device available: libscg has no CPU fallback");
+    }
+    if (!tl_devices.empty()) {
+        for (int v : tl_devices) {
+            if (v < 0 || v >= n) throw Error(SCG_ERR_DEVICE, "HIP device " + std::to_string(v) + " out of range (" + std::to_string(n) + " visible)");
+        }
+        if (explicit_list) *explicit_list = true;
+        return tl_devices;
+    }
+    std::vector<int> out;
+    const char* env = std::getenv("SCG_DEVICES");
+    if (explicit_list) *explicit_list = env && *env && std::strcmp(env, "all") != 0;
+    if (env && *env && std::strcmp(env, "all") != 0) {
+        const char* p = env;
+        while (*p) {
+            char* end = nullptr;
+            const long v = std::strtol(p, &end, 10);
+            if (end == p) throw Error(SCG_ERR_DEVICE, std::string("cannot parse SCG_DEVICES='") + env + "'");
+            if (v < 0 || v >= n) throw Error(SCG_ERR_DEVICE, "HIP device " + std::to_string(v) + " out of range (" + std::to_string(n) + " visible)");
+            out.push_back(static_cast<int>(v));
+            p = end;
+            while (*p == ',' || *p == ' ') ++p;
+        }
+        if (out.empty()) throw Error(SCG_ERR_DEVICE, "SCG_DEVICES lists no device");
+        return out;
+    }
+    const int first = resolve_device(-1);
+    const bool only_one = std::getenv("SCG_DEVICE") && *std::getenv("SCG_DEVICE") && !(env && *env);
+    out.push_back(first);
+    if (!only_one) for (int d = 0; d < n; ++d) if (d != first) out.push_back(d);
+    return out;
+}
+
+// Devices for ONE input of about `text_bytes` of FASTQ text: an explicit $SCG_DEVICES is taken as given; otherwise one
+// more device per four windows of text, so that small files do not pay for contexts and pinned buffers they cannot use.
+std::vector<int> devices_for_input(uint64_t text_bytes, size_t window) {
+    bool given = false;
+    std::vector<int> all = device_list(&given);
+    if (given) return all;
+    const uint64_t per_device = uint64_t(4) * window;
+    const size_t want = static_cast<size_t>(std::max<uint64_t>(1, text_bytes / per_device));
+    if (all.size() > want) all.resize(want);
+    return all;
+}
+
+uint64_t text_bytes_hint(const char* path) {
+    struct stat st;
+    if (!path || ::stat(path, &st) != 0) return 0;
+    unsigned char h[2] = {0, 0};
+    FILE* f = std::fopen(path, "rb");
+    size_t got = 0;
+    if (f) { got = std::fread(h, 1, 2, f); std::fclose(f); }
+    const bool gz = got == 2 && h[0] == 0x1f && h[1] == 0x8b;
+    return static_cast<uint64_t>(st.st_size) * (gz ? 5 : 1);
+}
+
+// A second plan with the same compiled (host-side) content, for another device.  Call before to_device().
+std::unique_ptr<scg_plan> clone_compiled(const scg_plan& a) {
+    std::unique_ptr<scg_plan> b(new scg_plan);
+    b->kind = a.kind;
+    b->ht1 = a.ht1; b->ht2 = a.ht2;
+    b->scan1 = a.scan1; b->scan2 = a.scan2;
+    b->htab[0] = a.htab[0]; b->htab[1] = a.htab[1];
+    b->hpairs = a.hpairs;
+    b->htab_combined = a.htab_combined;
+    b->n_pool[0] = a.n_pool[0]; b->n_pool[1] = a.n_pool[1];
+    b->max_mm1 = a.max_mm1; b->max_mm2 = a.max_mm2;
+    b->rev1 = a.rev1; b->rev2 = a.rev2; b->randomized = a.randomized; b->use_first = a.use_first;
+    b->diagnostics = a.diagnostics;
+    b->first1 = a.first1; b->first2 = a.first2;
+    b->n_counters = a.n_counters;
+    b->sparse = a.sparse;
+    return b;
+}
+
+// Files over devices inside one call (the matrixOf* functions: R/countSingleBarcodes.R:112-126, R/countComboBarcodes.R:149-164,
+// R/countDualBarcodes.R:205-254 hand the files to BiocParallel workers): every device runs one pipeline at a time and takes
+// the next unprocessed file when it is done; per_file(plan, i) counts file i and stores its column.  The error of the
+// lowest-numbered failing file is reported, as a serial loop over the files would.
+void schedule_files(int32_t n_files, const PlanSet& set, const std::function<void(scg_plan*, int32_t)>& per_file) {
+    std::atomic<int32_t> next(0), first_bad(n_files);
+    std::mutex mu;
+    int32_t bad = n_files;
+    int bad_code = 0;
+    std::string bad_msg;
+    auto worker = [&](scg_plan* P) {
+        for (;;) {
+            const int32_t i = next.fetch_add(1);
+            if (i >= n_files) return;
+            if (i > first_bad.load()) return;      // a file before this one has failed: the call reports that error, whatever comes after
+            int code = 0;
+            std::string msg;
+            try {
+                DeviceGuard g(P->device);
+                per_file(P, i);
+                continue;
+            } catch (const Error& e) { code = e.code; msg = e.what();
+            } catch (const std::bad_alloc&) { code = SCG_ERR_DEVICE; msg = "out of host memory";
+            } catch (const std::exception& e) { code = SCG_ERR_INVALID; msg = e.what(); }
+            std::lock_guard<std::mutex> g(mu);
+            if (i < bad) { bad = i; bad_code = code; bad_msg = msg; first_bad.store(i); }
+        }
+    };
+    std::vector<std::thread> th;
+    for (size_t d = 1; d < set.plans.size(); ++d) th.emplace_back(worker, set.plans[d].get());
+    worker(set.plans[0].get());
+    for (auto& t : th) t.join();
+    if (bad < n_files) throw Error(bad_code, bad_msg);
+}
+
+void combo_compact(const int32_t* cells, int32_t n0, int32_t n1, int32_t** indices_out, int32_t** freq_out, int64_t* k_out) {
+    int64_t total = static_cast<int64_t>(n0) * n1, k = 0;
+    for (int64_t c = 0; c < total; ++c) k += cells[c] != 0;
+    int32_t* idx = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * static_cast<size_t>(2 * k + 1)));
+    int32_t* freq = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * static_cast<size_t>(k + 1)));
+    if (!idx || !freq) { std::free(idx); std::free(freq); throw std::bad_alloc(); }
+    int64_t j = 0;
+    // cell order = (first, second) lexicographic order = the reference's sorted column order
+    for (int64_t c = 0; c < total; ++c) {
+        if (cells[c]) {
+            idx[2 * j] = static_cast<int32_t>(c / n1);
+            idx[2 * j + 1] = static_cast<int32_t>(c % n1);
+            freq[j] = cells[c];
+            ++j;
+        }
+    }
+    *indices_out = idx; *freq_out = freq; *k_out = k;
+}
+
+// Sparse mode: (first << 32 | second) -> count, as the reference's sorted run-length form (src/utils.h:14-45).
+void combos_from_sparse(const std::unordered_map<uint64_t, int64_t>& m, int32_t** indices_out, int32_t** freq_out, int64_t* k_out) {
+    std::vector<std::pair<uint64_t, int64_t> > rows(m.begin(), m.end());
+    std::sort(rows.begin(), rows.end());                    // key order = (first, second) order
+    const size_t k = rows.size();
+    int32_t* idx = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * (2 * k + 1)));
+    int32_t* freq = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * (k + 1)));
+    if (!idx || !freq) { std::free(idx); std::free(freq); throw std::bad_alloc(); }
+    for (size_t j = 0; j < k; ++j) {
+        if (rows[j].second > static_cast<int64_t>(INT32_MAX)) { std::free(idx); std::free(freq); throw Error(SCG_ERR_INVALID, "a count exceeds the 32-bit range of the count vectors"); }
+        idx[2 * j] = static_cast<int32_t>(rows[j].first >> 32);
+        idx[2 * j + 1] = static_cast<int32_t>(rows[j].first & 0xFFFFFFFFu);
+        freq[j] = static_cast<int32_t>(rows[j].second);
+    }
+    *indices_out = idx; *freq_out = freq; *k_out = static_cast<int64_t>(k);
+}
+
+// [n_pool valid][b1][b2][uid1 x uid2] -> the reference's outputs: invalid combinations by first pool
+// index, merged (several uids of one IUPAC barcode share an index), sorted by (first, second).
+// (sparse: the plan is in sparse mode and these are its combinations by sequence uid, in place of the dense cells)
+void diagnostics_from_counters(const scg_plan* P, const std::vector<int32_t>& all, int32_t* counts_out,
+                               int32_t** idx_out, int32_t** freq_out, int64_t* k_out, int32_t* b1, int32_t* b2,
+                               const std::unordered_map<uint64_t, int64_t>* sparse) {
+    const int32_t n_pool = P->n_pool[0];
+    if (counts_out) std::copy(all.begin(), all.begin() + n_pool, counts_out);
+    *b1 = all[n_pool];
+    *b2 = all[n_pool + 1];
+    const int32_t* cells = all.data() + n_pool + 2;
+    const size_t nu1 = P->first1.size(), nu2 = P->first2.size();
+    std::vector<std::pair<std::pair<int32_t, int32_t>, int32_t> > found;
+    if (sparse) {
+        for (auto& kv : *sparse) {
+            const size_t u1 = static_cast<size_t>(kv.first >> 32), u2 = static_cast<size_t>(kv.first & 0xFFFFFFFFu);
+            if (u1 >= nu1 || u2 >= nu2) throw Error(SCG_ERR_DEVICE, "internal: combination out of range");
+            if (kv.second > static_cast<int64_t>(INT32_MAX)) throw Error(SCG_ERR_INVALID, "a count exceeds the 32-bit range of the count vectors");
+            found.push_back(std::make_pair(std::make_pair(P->first1[u1], P->first2[u2]), static_cast<int32_t>(kv.second)));
+        }
+    } else {
+        for (size_t u1 = 0; u1 < nu1; ++u1) {
+            for (size_t u2 = 0; u2 < nu2; ++u2) {
+                int32_t c = cells[u1 * nu2 + u2];
+                if (c) found.push_back(std::make_pair(std::make_pair(P->first1[u1], P->first2[u2]), c));
+            }
+        }
+    }
+    std::sort(found.begin(), found.end());
+    std::vector<int32_t> idx, freq;
+    for (size_t i = 0; i < found.size(); ++i) {
+        if (i && found[i].first == found[i - 1].first) {
+            freq.back() += found[i].second;
+        } else {
+            idx.push_back(found[i].first.first);
+            idx.push_back(found[i].first.second);
+            freq.push_back(found[i].second);
+        }
+    }
+    int32_t* oi = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * (idx.size() + 1)));
+    int32_t* of = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * (freq.size() + 1)));
+    if (!oi || !of) { std::free(oi); std::free(of); throw std::bad_alloc(); }
+    std::copy(idx.begin(), idx.end(), oi);
+    std::copy(freq.begin(), freq.end(), of);
+    *idx_out = oi; *freq_out = of; *k_out = static_cast<int64_t>(freq.size());
+}
+
+PlanSet::PlanSet(std::unique_ptr<scg_plan> compiled, const std::vector<int>& devices) {
+    for (size_t i = 1; i < devices.size(); ++i) plans.push_back(clone_compiled(*compiled));
+    plans.insert(plans.begin(), std::move(compiled));
+    for (size_t i = 0; i < plans.size(); ++i) plans[i]->to_device(devices[i]);
+}
+std::vector<scg_plan*> PlanSet::all() const {
+    std::vector<scg_plan*> v;
+    for (auto& p : plans) v.push_back(p.get());
+    return v;
+}
+int64_t PlanSet::total() const {
+    int64_t t = 0;
+    for (auto& p : plans) t += p->total;
+    return t;
+}
+void PlanSet::read(int32_t* counts_out) const {
+    if (plans.size() == 1) {
+        DeviceGuard g(plans[0]->device);
+        read_counters(plans[0].get(), counts_out);
+        return;
+    }
+    const size_t n = static_cast<size_t>(plans[0]->n_counters);
+    std::vector<int64_t> acc(n, 0);
+    std::vector<int32_t> part(n + 1);
+    for (auto& p : plans) {
+        DeviceGuard g(p->device);
+        read_counters(p.get(), part.data());
+        for (size_t i = 0; i < n; ++i) acc[i] += part[i];
+    }
+    if (counts_out) {
+        for (size_t i = 0; i < n; ++i) {
+            if (acc[i] > static_cast<int64_t>(INT32_MAX)) throw Error(SCG_ERR_INVALID, "a count exceeds the 32-bit range of the count vectors");
+            counts_out[i] = static_cast<int32_t>(acc[i]);
+        }
+    }
+}
+void PlanSet::reset() const { for (auto& p : plans) reset_plan(p.get()); }
+std::unordered_map<uint64_t, int64_t> PlanSet::sparse_merged() const {
+    std::unordered_map<uint64_t, int64_t> all;
+    for (auto& p : plans) {
+        retire_all_pairs(p.get());
+        if (all.empty()) all = p->sparse_counts;
+        else for (auto& kv : p->sparse_counts) all[kv.first] += kv.second;
+    }
+    return all;
+}
+
+void set_thread_devices(const int* devices, int32_t n) { tl_devices.assign(devices, devices + n); }
+
+} // namespace scgapi

@@ -649,3 +649,165 @@ def test_paired_ordinary_gzip_mates_decoded_by_the_device(sc, oracle, gpu, tmp_p
                                           second, case["template2"], case["reverse2"], case["mismatches2"], case["pool2"],
                                           case["randomized"], case["use_first"], False, 4)
             assert t == exp[1] and np.array_equal(c, exp[0]), (second, window_kb)
+
+
+# ---- the fall-back ladders (csrc/scg_files.cpp): one line per rung entered and per decline under SCG_TRACE=1 ----
+def rung_lines(capfd):
+    return [line[len("[scg] rung "):] for line in capfd.readouterr().err.splitlines() if line.startswith("[scg] rung ")]
+
+
+def bgzf_with_a_named_member(path, text, block, named):
+    """BGZF whose member number `named` carries a file name as well (FLG = FEXTRA | FNAME): gzip that zlib reads, but not the
+    FEXTRA-only header the device's inflater takes -- the device declines the file, the host threads inflate it."""
+    import struct
+    import zlib
+    out = []
+    chunks = [text[i:i + block] for i in range(0, len(text), block)] + [b""]          # (the last: bgzip's end-of-file marker)
+    for k, chunk in enumerate(chunks):
+        c = zlib.compressobj(6, zlib.DEFLATED, -15)
+        payload = c.compress(chunk) + c.flush()
+        name = b"reads.fastq\0" if k == named else b""
+        size = 18 + len(name) + len(payload) + 8
+        out.append(b"\x1f\x8b\x08" + (b"\x0c" if name else b"\x04") + b"\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", size - 1) + name +
+                   payload + struct.pack("<II", zlib.crc32(chunk) & 0xFFFFFFFF, len(chunk)))
+    open(path, "wb").write(b"".join(out))
+    return len(chunks) - 1
+
+
+def with_a_multi_line_record(reads, at):
+    """FASTQ text whose record number `at` has its sequence and quality on two lines each: legal for the reference
+    (FastqReader.hpp:66-84), declined by the record scans."""
+    r = reads[at]
+    assert len(r) >= 2
+    multi = b"@r%d\n" % at + r[:len(r) // 2].encode() + b"\n" + r[len(r) // 2:].encode() + b"\n+\n" + b"I" * (len(r) // 2) + b"\n" + b"I" * (len(r) - len(r) // 2) + b"\n"
+    return gen.fastq_text(reads[:at]) + multi + gen.fastq_text(reads[at + 1:])
+
+
+DECLINED_INFLATE = ["device-inflate", "device-inflate: declined -> host-threads", "host-threads"]
+DECLINED_SCAN = ["host-threads", "host-threads: declined -> host-reader", "host-reader"]
+DECLINED_MATE = ["device-mates", "device-mates: declined -> host-threads", "host-threads"]
+PARALLEL_GZIP = ["host-threads", ("host-threads: declined -> single-stream", "single-stream")]      # (the pair: optional)
+SINGLE_RUNGS = [      # input, where its flaw sits, the rungs of a one-file entry, those of a many-files entry
+    ("plain", None, ["host-threads"], ["host-threads"]),
+    ("bgzf", None, ["device-inflate"], ["device-inflate"]),
+    ("gzip", None, ["device-gunzip"], ["host-threads"]),
+    ("bgzf named member", "first", DECLINED_INFLATE, DECLINED_INFLATE),
+    ("bgzf named member", "late", DECLINED_INFLATE, DECLINED_INFLATE),
+    # (members smaller than its chunks: the parallel gzip decoder of the host threads may hand the file on to the one inflate stream)
+    ("gzip many small members", None, ["device-gunzip: declined -> host-threads"] + PARALLEL_GZIP, PARALLEL_GZIP),
+    ("plain multi-line record", "first", DECLINED_SCAN, DECLINED_SCAN),
+    ("plain multi-line record", "late", DECLINED_SCAN, DECLINED_SCAN),
+]
+
+
+@pytest.mark.parametrize("entry", ["one_file", "many_files"])
+@pytest.mark.parametrize("case", SINGLE_RUNGS, ids=[f"{c[0]} {c[1]}" if c[1] else c[0] for c in SINGLE_RUNGS])
+def test_single_end_rungs(sc, oracle, gpu, tmp_path, monkeypatch, capfd, case, entry):
+    """One rule for every decline, in the first window or behind many (8 KB windows over ~1 MB of text): the pipeline goes, the
+    plans are reset, the next rung that applies takes the file -- the same rungs in the same order from both kinds of entry
+    (only the one-file entries have the device's gzip decoder), and the oracle's counts at the end."""
+    import zlib
+    form, where, one_file, many_files = case
+    pool, reads = make_case(41, n=30000 if form.startswith("gzip") else 6000)
+    reads = [r if len(r) >= 2 else "AC" for r in reads]
+    exp, total = oracle.count_single(reads, TEMPLATE, 2, pool, 1, True)
+    text = gen.fastq_text(reads)
+    path = str(tmp_path / ("r.fastq" if form.startswith("plain") else "r.fastq.gz"))
+    if where:
+        monkeypatch.setenv("SCG_WINDOW_KB", "8")
+    if form == "plain":
+        open(path, "wb").write(text)
+    elif form == "bgzf":
+        gen.write_bgzf(path, text, block=3000)
+    elif form == "bgzf named member":
+        n = bgzf_with_a_named_member(path, text, 3000, 0)
+        if where == "late":
+            assert n >= 200                                                # (two or three members to a window)
+            bgzf_with_a_named_member(path, text, 3000, n // 2)
+    elif form == "plain multi-line record":
+        open(path, "wb").write(with_a_multi_line_record(reads, 0 if where == "first" else len(reads) // 2))
+    else:
+        monkeypatch.setenv("SCG_PGZIP_CHUNK_KB", "64")                     # (these files are small: let the chunked decoders have them)
+        monkeypatch.setenv("SCG_DGZIP_CHUNK_KB", "16")
+        pieces = [text] if form == "gzip" else [text[i:i + 50000] for i in range(0, len(text), 50000)]
+        data = b""
+        for piece in pieces:
+            c = zlib.compressobj(6, zlib.DEFLATED, 31)
+            data += c.compress(piece) + c.flush()
+        open(path, "wb").write(data)
+    monkeypatch.setenv("SCG_TRACE", "1")
+    capfd.readouterr()
+    if entry == "one_file":
+        got, n = sc.count_single_barcodes(path, TEMPLATE, 2, pool, 1, True, 4)
+    else:                                                                  # (a list of one file takes the one-file entry)
+        mat, tot = sc.count_single_barcodes_files([path, path], TEMPLATE, 2, pool, 1, True, 4, [0])
+        assert tot[0] == tot[1] and np.array_equal(mat[:, 0], mat[:, 1])
+        got, n = mat[:, 0], tot[0]
+    rungs = rung_lines(capfd)
+    print(case[:2], entry, rungs)
+    expected = one_file if entry == "one_file" else many_files * 2
+    if isinstance(expected[-1], tuple):
+        walks = [[x for x in expected if not isinstance(x, tuple)], [y for x in expected for y in (x if isinstance(x, tuple) else (x,))]]
+        assert rungs in walks
+    else:
+        assert rungs == expected
+    assert n == total == len(reads) and np.array_equal(got, exp)
+
+
+PAIRED_RUNGS = [      # mate 2, where its flaw sits, SCG_DEVICE_INFLATE, the rungs
+    ("plain", None, "1", ["host-threads"]),
+    ("bgzf", None, "2", ["device-mates"]),
+    ("bgzf named member", "first", "1", DECLINED_MATE),
+    ("bgzf named member", "late", "1", DECLINED_MATE),
+    ("bgzf named member", "first", "2", DECLINED_MATE[:2]),
+    ("bgzf named member", "late", "2", DECLINED_MATE[:2]),
+]
+
+
+@pytest.mark.parametrize("entry", ["one_file", "many_files"])
+@pytest.mark.parametrize("case", PAIRED_RUNGS, ids=[" ".join(x for x in c[:3] if x) for c in PAIRED_RUNGS])
+def test_paired_rungs(sc, oracle, gpu, tmp_path, monkeypatch, capfd, case, entry):
+    """The same rule for paired input: a BGZF mate the device declines -- in its first window or behind many -- is inflated by
+    the host threads next, and SCG_DEVICE_INFLATE=2 makes that decline an error, wherever it happens and whichever entry
+    the files came through."""
+    from screencounter_amd import _lib
+    form, where, inflate, expected = case
+    pool, reads = make_case(42)
+    exp, total = oracle.count_dual(reads, reads, TEMPLATE, False, 1, pool, TEMPLATE, False, 1, pool, False, True)
+    text = gen.fastq_text(reads)
+    p1, p2 = str(tmp_path / "m1.fastq"), str(tmp_path / ("m2.fastq" if form == "plain" else "m2.fastq.gz"))
+    open(p1, "wb").write(text)
+    if where:
+        monkeypatch.setenv("SCG_WINDOW_KB", "8")
+    if form == "plain":
+        open(p2, "wb").write(text)
+    elif form == "bgzf":
+        gen.write_bgzf(p2, text, block=3000)
+    else:
+        n = bgzf_with_a_named_member(p2, text, 3000, 0)
+        if where == "late":
+            assert n >= 200
+            bgzf_with_a_named_member(p2, text, 3000, n // 2)
+    monkeypatch.setenv("SCG_DEVICE_INFLATE", inflate)
+    monkeypatch.setenv("SCG_TRACE", "1")
+
+    def count():
+        if entry == "one_file":
+            return sc.count_dual_barcodes(p1, TEMPLATE, False, 1, pool, p2, TEMPLATE, False, 1, pool, False, True, False, 4)
+        # (a list of one pair takes the one-file entry; the one device takes the pairs in turn and stops at the first error)
+        mat, tot = sc.count_dual_barcodes_files([p1, p1], TEMPLATE, False, 1, pool, [p2, p2], TEMPLATE, False, 1, pool, False, True, 4, [0])
+        assert tot[0] == tot[1] and np.array_equal(mat[:, 0], mat[:, 1])
+        return mat[:, 0], tot[0]
+
+    capfd.readouterr()
+    strict = bool(where) and inflate == "2"
+    if strict:
+        with pytest.raises(_lib.ScgError) as e:
+            count()
+        assert e.value.code == _lib.SCG_ERR_UNSUPPORTED and "SCG_DEVICE_INFLATE=2" in str(e.value)
+    else:
+        got, n = count()
+        assert n == total == len(reads) and np.array_equal(got, exp)
+    rungs = rung_lines(capfd)
+    print(case[:3], entry, rungs)
+    assert rungs == expected * (1 if strict or entry == "one_file" else 2)

@@ -331,7 +331,7 @@ def test_several_plans_of_one_call(sc, oracle, gpu, tmp_path, monkeypatch, scan,
 @pytest.mark.parametrize("form", ["bgzf", "gzip"])
 def test_compressed_forms_of_the_same_text(sc, oracle, gpu, tmp_path, monkeypatch, scan, form):
     """The flawed text as BGZF and as ordinary gzip: the device inflater and scan decline it, then the host readers; the
-    plans are reset by those fall-backs (count_single_end, compile_and_count_*) before the sequential reader takes the file."""
+    plans are reset by those fall-backs (the ladders of csrc/scg_files.cpp) before the sequential reader takes the file."""
     monkeypatch.setenv("SCG_HOST_THREADS", str(HOST_THREADS))
     for storage in ("dense", "sparse"):
         grid_storage(monkeypatch, storage)

@@ -69,8 +69,16 @@ def test_the_flaws_sit_behind_many_windows(tmp_path):
 
 def test_restarts_clear_the_plan_through_reset_plan():
     """A restart that clears only the dense counters leaves the combinations of sparse mode (and batches still in flight)
-    behind: every clear of a plan's counters in the pipelines goes through reset_plan."""
-    text = open(os.path.join(ROOT, "screencounter_amd", "csrc", "scg_pipelines.cpp")).read()
+    behind: every clear of a plan's counters in the host sources goes through reset_plan.  (scg_plan_reset, the ABI's own reset,
+    is no restart: it clears on the caller's stream, in the caller's order, and is left out.)"""
+    import glob
+    csrc = os.path.join(ROOT, "screencounter_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.cpp")) + glob.glob(os.path.join(csrc, "*.hpp")))
+    assert len(files) >= 8, files
+    text = "".join(open(f).read() for f in files)
+    abi = re.search(r"^int scg_plan_reset\(.*?^\}\n", text, re.S | re.M)
+    assert abi and abi.group(0).count("sparse_counts.clear()") == 1, "scg_plan_reset not found"
+    text = text[:abi.start()] + text[abi.end():]
     m = re.search(r"^void reset_plan\(scg_plan\* P\) \{\n(.*?)^\}\n", text, re.S | re.M)
     assert m, "reset_plan not found"
     outside = text[:m.start()] + text[m.end():]
