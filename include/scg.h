@@ -225,6 +225,54 @@ int scg_count_dual_barcodes_files(const char* const* paths1, const char* constan
                                   int32_t* counts_out, int32_t* totals_out,
                                   char* err, size_t errcap);
 
+/* The four entries below -- matrixOfDualBarcodes(include.invalid=TRUE), matrixOfDualBarcodesSingleEnd with and without
+ * include.invalid (R/countDualBarcodesSingleEnd.R) and matrixOfPairedComboBarcodes (R/countPairedComboBarcodes.R) -- keep
+ * the contract above and state the rest of it: argument errors are SCG_ERR_INVALID (SCG_ERR_UNSUPPORTED) with the message
+ * of the one-file entry, raised before any file is opened and any device is touched; n_files == 0 succeeds and writes
+ * nothing; where an entry has per-file malloc'd outputs (arrays of n_files entries as in
+ * scg_count_combo_barcodes_single_files), entry f receives what the one-file entry returns for file f, and on ANY error
+ * every buffer handed out so far has been freed and the arrays are all-NULL (k_out all 0): there is never anything to free
+ * after a failed call. */
+
+/* counts_out: n_pool x n_files, column-major; invalid_indices_out / invalid_freq_out / k_out: per file, as
+ * scg_count_dual_barcodes_diagnostics returns them (release every entry with scg_free); totals_out, barcode1_only_out,
+ * barcode2_only_out: n_files entries each. */
+int scg_count_dual_barcodes_diagnostics_files(const char* const* paths1, const char* constant1, int reverse1, int mismatches1,
+                                              const char* const* pool1,
+                                              const char* const* paths2, const char* constant2, int reverse2, int mismatches2,
+                                              const char* const* pool2, int32_t n_pool, int32_t n_files,
+                                              int randomized, int use_first, int nthreads,
+                                              int32_t* counts_out, int32_t** invalid_indices_out, int32_t** invalid_freq_out,
+                                              int64_t* k_out, int32_t* totals_out,
+                                              int32_t* barcode1_only_out, int32_t* barcode2_only_out,
+                                              char* err, size_t errcap);
+
+/* Per file what scg_count_dual_barcodes_single_end gives with diagnostics = 0.  counts_out: n_pools[0] x n_files,
+ * column-major; totals_out: n_files. */
+int scg_count_dual_barcodes_single_end_files(const char* const* paths, int32_t n_files, const char* constant,
+                                             const char* const* const* pools, const int32_t* n_pools, int32_t n_regions,
+                                             int strand, int mismatches, int use_first, int nthreads,
+                                             int32_t* counts_out, int32_t* totals_out, char* err, size_t errcap);
+
+/* counts_out: n_pools[0] x n_files, column-major; invalid_indices_out / invalid_freq_out / k_out: per file, as
+ * scg_count_dual_barcodes_single_end_diagnostics returns them (release every entry with scg_free); totals_out: n_files. */
+int scg_count_dual_barcodes_single_end_diagnostics_files(const char* const* paths, int32_t n_files, const char* constant,
+                                                         const char* const* const* pools, const int32_t* n_pools, int32_t n_regions,
+                                                         int strand, int mismatches, int use_first, int nthreads,
+                                                         int32_t* counts_out, int32_t** invalid_indices_out, int32_t** invalid_freq_out,
+                                                         int64_t* k_out, int32_t* totals_out, char* err, size_t errcap);
+
+/* indices_out / freq_out / k_out: per file, as scg_count_combo_barcodes_paired returns them (release every entry with
+ * scg_free); totals_out, barcode1_only_out, barcode2_only_out: n_files entries each. */
+int scg_count_combo_barcodes_paired_files(const char* const* paths1, const char* constant1, int reverse1, int mismatches1,
+                                          const char* const* pool1, int32_t n_pool1,
+                                          const char* const* paths2, const char* constant2, int reverse2, int mismatches2,
+                                          const char* const* pool2, int32_t n_pool2, int32_t n_files,
+                                          int randomized, int use_first, int nthreads,
+                                          int32_t** indices_out, int32_t** freq_out, int64_t* k_out,
+                                          int32_t* totals_out, int32_t* barcode1_only_out, int32_t* barcode2_only_out,
+                                          char* err, size_t errcap);
+
 /* matchBarcodes.  Replaces src/match_barcodes.cpp:6-37.  index_out[i] is the 0-based index of the
  * unique best choice within `substitutions` mismatches or -1 (R: NA); mismatches_out likewise. */
 int scg_match_barcodes(const char* const* sequences, int32_t n_sequences,

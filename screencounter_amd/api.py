@@ -119,9 +119,7 @@ def count_combo_barcodes_single_files(paths: Sequence[str], constant: str, stran
         raise ScgError(_lib.SCG_ERR_INVALID, "currently expecting only 2 variable regions for single-end combinatorial barcodes")
     L = _lib.load()
     n = len(paths)
-    idx = (_lib.i32_p * max(n, 1))()
-    freq = (_lib.i32_p * max(n, 1))()
-    ks = (C.c_int64 * max(n, 1))()
+    idx, freq, ks = _per_file_arrays(n)
     totals = (C.c_int32 * max(n, 1))()
     err = errbuf()
     p0, _k0 = cstr_array(pool[0])
@@ -131,13 +129,24 @@ def count_combo_barcodes_single_files(paths: Sequence[str], constant: str, stran
         check(L.scg_count_combo_barcodes_single_files(farr, n, constant.encode(), int(strand), p0, len(pool[0]), p1, len(pool[1]),
                                                       int(mismatches), int(bool(use_first)), int(nthreads), idx, freq, ks, totals,
                                                       err, _lib.ERRCAP), err)
+    return [(i2, fr, int(totals[f])) for f, (i2, fr) in enumerate(_take_per_file(L, idx, freq, ks, n))]
+
+
+def _per_file_arrays(n: int):
+    """Caller-allocated arrays of n entries for the per-file malloc'd outputs of a many-files entry (2 x K_f indices, K_f
+    frequencies, K_f)."""
+    return (_lib.i32_p * max(n, 1))(), (_lib.i32_p * max(n, 1))(), (C.c_int64 * max(n, 1))()
+
+
+def _take_per_file(L, idx, freq, ks, n: int):
+    """Those outputs as a list of (indices int32[2, K_f], freq int32[K_f]), released on the C side whatever happens."""
     out = []
     try:
         for f in range(n):
             K = int(ks[f])
             i2 = np.ctypeslib.as_array(idx[f], shape=(max(2 * K, 1),))[:2 * K].reshape(K, 2).T.copy() if K else np.zeros((2, 0), dtype=np.int32)
             fr = np.ctypeslib.as_array(freq[f], shape=(max(K, 1),))[:K].copy() if K else np.zeros(0, dtype=np.int32)
-            out.append((i2.astype(np.int32), fr.astype(np.int32), int(totals[f])))
+            out.append((i2.astype(np.int32), fr.astype(np.int32)))
     finally:
         for f in range(n):
             L.scg_free(idx[f])
@@ -168,6 +177,101 @@ def count_dual_barcodes_files(paths1: Sequence[str], constant1: str, reverse1: b
                                               int(bool(randomized)), int(bool(use_first)), int(nthreads),
                                               _files_out(counts, len(pool1)), totals, err, _lib.ERRCAP), err)
     return _files_matrix(counts, len(pool1), n), [int(totals[i]) for i in range(n)]
+
+
+def count_dual_barcodes_diagnostics_files(paths1: Sequence[str], constant1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],
+                                          paths2: Sequence[str], constant2: str, reverse2: bool, mismatches2: int, pool2: Sequence[str],
+                                          randomized: bool, use_first: bool, nthreads: int = 1, devices=None):
+    """scg_count_dual_barcodes_diagnostics_files: every pair of files of matrixOfDualBarcodes(include.invalid=TRUE) in one
+    native call -> (counts int32[len(pool1), n_files], list of (indices int32[2, K], freq int32[K]) per file, totals list,
+    barcode1_only list, barcode2_only list)."""
+    if len(pool1) != len(pool2):
+        raise ScgError(_lib.SCG_ERR_INVALID, "both barcode pools should be of the same length")
+    if len(paths1) != len(paths2):
+        raise ValueError("paths1 and paths2 differ in length")
+    L = _lib.load()
+    n = len(paths1)
+    counts = np.zeros((max(n, 1), max(len(pool1), 1)), dtype=np.int32)
+    idx, freq, ks = _per_file_arrays(n)
+    totals, b1, b2 = (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))()
+    err = errbuf()
+    a1, _k1 = cstr_array(pool1)
+    a2, _k2 = cstr_array(pool2)
+    f1, _fk1 = cstr_array([os.fspath(x) for x in paths1])
+    f2, _fk2 = cstr_array([os.fspath(x) for x in paths2])
+    with _devices_env(devices):
+        check(L.scg_count_dual_barcodes_diagnostics_files(f1, constant1.encode(), int(bool(reverse1)), int(mismatches1), a1,
+                                                          f2, constant2.encode(), int(bool(reverse2)), int(mismatches2), a2, len(pool1), n,
+                                                          int(bool(randomized)), int(bool(use_first)), int(nthreads),
+                                                          _files_out(counts, len(pool1)), idx, freq, ks, totals, b1, b2,
+                                                          err, _lib.ERRCAP), err)
+    invalid = _take_per_file(L, idx, freq, ks, n)
+    return (_files_matrix(counts, len(pool1), n), invalid, [int(totals[i]) for i in range(n)],
+            [int(b1[i]) for i in range(n)], [int(b2[i]) for i in range(n)])
+
+
+def count_dual_barcodes_single_end_files(paths: Sequence[str], constant: str, pools: Sequence[Sequence[str]], strand: int, mismatches: int,
+                                         use_first: bool, nthreads: int = 1, devices=None):
+    """scg_count_dual_barcodes_single_end_files: every file of matrixOfDualBarcodesSingleEnd in one native call
+    -> (counts int32[n combinations, n_files], totals list)."""
+    L = _lib.load()
+    n = len(paths)
+    nch = len(pools[0]) if pools else 0
+    counts = np.zeros((max(n, 1), max(nch, 1)), dtype=np.int32)
+    totals = (C.c_int32 * max(n, 1))()
+    err = errbuf()
+    rows, sizes, _keep = _lib.cstr_matrix(pools)
+    farr, _fk = cstr_array([os.fspath(x) for x in paths])
+    with _devices_env(devices):
+        check(L.scg_count_dual_barcodes_single_end_files(farr, n, constant.encode(), rows, sizes, len(pools), int(strand), int(mismatches),
+                                                         int(bool(use_first)), int(nthreads), _files_out(counts, nch), totals,
+                                                         err, _lib.ERRCAP), err)
+    return _files_matrix(counts, nch, n), [int(totals[i]) for i in range(n)]
+
+
+def count_dual_barcodes_single_end_diagnostics_files(paths: Sequence[str], constant: str, pools: Sequence[Sequence[str]], strand: int,
+                                                     mismatches: int, use_first: bool, nthreads: int = 1, devices=None):
+    """scg_count_dual_barcodes_single_end_diagnostics_files: matrixOfDualBarcodesSingleEnd(include.invalid=TRUE) in one native
+    call -> (counts int32[n combinations, n_files], list of (indices int32[2, K], freq int32[K]) per file, totals list)."""
+    L = _lib.load()
+    n = len(paths)
+    nch = len(pools[0]) if pools else 0
+    counts = np.zeros((max(n, 1), max(nch, 1)), dtype=np.int32)
+    idx, freq, ks = _per_file_arrays(n)
+    totals = (C.c_int32 * max(n, 1))()
+    err = errbuf()
+    rows, sizes, _keep = _lib.cstr_matrix(pools)
+    farr, _fk = cstr_array([os.fspath(x) for x in paths])
+    with _devices_env(devices):
+        check(L.scg_count_dual_barcodes_single_end_diagnostics_files(farr, n, constant.encode(), rows, sizes, len(pools), int(strand),
+                                                                     int(mismatches), int(bool(use_first)), int(nthreads),
+                                                                     _files_out(counts, nch), idx, freq, ks, totals, err, _lib.ERRCAP), err)
+    invalid = _take_per_file(L, idx, freq, ks, n)
+    return _files_matrix(counts, nch, n), invalid, [int(totals[i]) for i in range(n)]
+
+
+def count_combo_barcodes_paired_files(paths1: Sequence[str], constant1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],
+                                      paths2: Sequence[str], constant2: str, reverse2: bool, mismatches2: int, pool2: Sequence[str],
+                                      randomized: bool, use_first: bool, nthreads: int = 1, devices=None):
+    """scg_count_combo_barcodes_paired_files: every pair of files of matrixOfPairedComboBarcodes in one native call
+    -> list of (indices int32[2, K], freq int32[K], total, barcode1_only, barcode2_only), one per pair of files."""
+    if len(paths1) != len(paths2):
+        raise ValueError("paths1 and paths2 differ in length")
+    L = _lib.load()
+    n = len(paths1)
+    idx, freq, ks = _per_file_arrays(n)
+    totals, b1, b2 = (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))()
+    err = errbuf()
+    a1, _k1 = cstr_array(pool1)
+    a2, _k2 = cstr_array(pool2)
+    f1, _fk1 = cstr_array([os.fspath(x) for x in paths1])
+    f2, _fk2 = cstr_array([os.fspath(x) for x in paths2])
+    with _devices_env(devices):
+        check(L.scg_count_combo_barcodes_paired_files(f1, constant1.encode(), int(bool(reverse1)), int(mismatches1), a1, len(pool1),
+                                                      f2, constant2.encode(), int(bool(reverse2)), int(mismatches2), a2, len(pool2), n,
+                                                      int(bool(randomized)), int(bool(use_first)), int(nthreads),
+                                                      idx, freq, ks, totals, b1, b2, err, _lib.ERRCAP), err)
+    return [(i2, fr, int(totals[f]), int(b1[f]), int(b2[f])) for f, (i2, fr) in enumerate(_take_per_file(L, idx, freq, ks, n))]
 
 
 def count_dual_barcodes(path1: str, constant1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],

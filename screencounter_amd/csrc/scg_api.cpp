@@ -465,12 +465,7 @@ int scg_count_dual_barcodes_diagnostics(const char* path1, const char* constant1
         auto set = compile_and_count_paired(path1, path2, fq1, fq2, nthreads, [&] {
             return compile_dual(constant1, reverse1, mismatches1, pool1, constant2, reverse2, mismatches2, pool2, n_pool, randomized, use_first, 1);
         });
-        std::vector<int32_t> all(static_cast<size_t>(set->first()->n_counters) + 1);
-        set->read(all.data());
-        const auto sparse = set->first()->sparse ? set->sparse_merged() : std::unordered_map<uint64_t, int64_t>();
-        diagnostics_from_counters(set->first(), all, counts_out, invalid_indices_out, invalid_freq_out, k_out, barcode1_only_out, barcode2_only_out,
-                                  set->first()->sparse ? &sparse : nullptr);
-        *total_out = narrow_total(set->total());
+        result_diagnostics(set->all(), counts_out, invalid_indices_out, invalid_freq_out, k_out, total_out, barcode1_only_out, barcode2_only_out);
     });
 }
 
@@ -487,8 +482,7 @@ int scg_count_dual_barcodes_single_end(const char* path, const char* constant, c
             }
             return P;
         });
-        set->read(counts_out);
-        *total_out = narrow_total(set->total());
+        result_counts(set->all(), counts_out, total_out);
     });
 }
 
@@ -592,13 +586,7 @@ int scg_count_dual_barcodes_single_end_diagnostics(const char* path, const char*
         auto set = compile_and_count_single_end(path, fq, nthreads, [&] {
             return compile_dual_single_end_diag(constant, strand, pools, n_pools, n_regions, mismatches, use_first);
         });
-        std::vector<int32_t> all(static_cast<size_t>(set->first()->n_counters) + 1);
-        set->read(all.data());
-        const int32_t total = narrow_total(set->total());
-        int32_t b1 = 0, b2 = 0;
-        const auto sparse = set->first()->sparse ? set->sparse_merged() : std::unordered_map<uint64_t, int64_t>();
-        diagnostics_from_counters(set->first(), all, counts_out, invalid_indices_out, invalid_freq_out, k_out, &b1, &b2, set->first()->sparse ? &sparse : nullptr);
-        *total_out = total;
+        result_diagnostics(set->all(), counts_out, invalid_indices_out, invalid_freq_out, k_out, total_out, nullptr, nullptr);
     });
 }
 
@@ -620,12 +608,7 @@ int scg_count_combo_barcodes_paired(const char* path1, const char* constant1, in
             return compile_paired_combo(constant1, reverse1, mismatches1, pool1, n_pool1, constant2, reverse2, mismatches2, pool2, n_pool2,
                                         randomized, use_first);
         });
-        std::vector<int32_t> all(static_cast<size_t>(set->first()->n_counters) + 1);
-        set->read(all.data());
-        const auto sparse = set->first()->sparse ? set->sparse_merged() : std::unordered_map<uint64_t, int64_t>();
-        diagnostics_from_counters(set->first(), all, nullptr, indices_out, freq_out, k_out, barcode1_only_out, barcode2_only_out,
-                                  set->first()->sparse ? &sparse : nullptr);
-        *total_out = narrow_total(set->total());
+        result_diagnostics(set->all(), nullptr, indices_out, freq_out, k_out, total_out, barcode1_only_out, barcode2_only_out);
     });
 }
 
@@ -645,14 +628,10 @@ int scg_count_single_barcodes_files(const char* const* paths, int32_t n_files, c
             return;
         }
         scg::FastqStream probe(paths[0]);                          // the first file's reader comes before the argument checks, as in a loop over files
-        std::vector<int> devices = device_list();
-        if (devices.size() > static_cast<size_t>(n_files)) devices.resize(static_cast<size_t>(n_files));
+        const std::vector<int> devices = devices_for_files(n_files);
         PlanSet set(compile_single(constant, strand, pool, n_pool, mismatches, use_first), devices);
         const size_t stride = static_cast<size_t>(n_pool);
-        schedule_files(n_files, set, [&](scg_plan* P, int32_t f) {
-            scg::FastqStream fq(paths[f]);
-            reset_plan(P);
-            count_single_end(std::vector<scg_plan*>(1, P), paths[f], fq, nthreads);
+        schedule_single_end(n_files, set, paths, nthreads, [&](scg_plan* P, int32_t f) {
             read_counters(P, counts_out + stride * static_cast<size_t>(f));
             totals_out[f] = narrow_total(P->total);
         });
@@ -666,31 +645,21 @@ int scg_count_combo_barcodes_single_files(const char* const* paths, int32_t n_fi
                                           char* err, size_t errcap) {
     return guarded(err, errcap, [&] {
         if (n_files < 0 || (n_files > 0 && (!paths || !indices_out || !freq_out || !k_out || !totals_out))) throw Error(SCG_ERR_INVALID, "null argument");
-        for (int32_t f = 0; f < n_files; ++f) {
-            if (!paths[f]) throw Error(SCG_ERR_INVALID, "null argument");
-            indices_out[f] = nullptr; freq_out[f] = nullptr; k_out[f] = 0;
-        }
-        if (n_files == 0) return;
-        try {
+        with_per_file_outputs(indices_out, freq_out, k_out, n_files, [&] {
+            for (int32_t f = 0; f < n_files; ++f) if (!paths[f]) throw Error(SCG_ERR_INVALID, "null argument");
+            if (n_files == 0) return;
             scg::FastqStream probe(paths[0]);
-            std::vector<int> devices = device_list();
-            if (devices.size() > static_cast<size_t>(n_files)) devices.resize(static_cast<size_t>(n_files));
+            const std::vector<int> devices = devices_for_files(n_files);
             PlanSet set(compile_combo(constant, strand, pool0, n_pool0, pool1, n_pool1, mismatches, use_first), devices);
             const size_t cells = static_cast<size_t>(set.first()->n_counters);
-            schedule_files(n_files, set, [&](scg_plan* P, int32_t f) {
-                scg::FastqStream fq(paths[f]);
-                reset_plan(P);
-                count_single_end(std::vector<scg_plan*>(1, P), paths[f], fq, nthreads);
+            schedule_single_end(n_files, set, paths, nthreads, [&](scg_plan* P, int32_t f) {
                 std::vector<int32_t> dense(cells + 1);
                 read_counters(P, dense.data());
                 totals_out[f] = narrow_total(P->total);
                 if (P->sparse) { retire_all_pairs(P); combos_from_sparse(P->sparse_counts, &indices_out[f], &freq_out[f], &k_out[f]); }
                 else combo_compact(dense.data(), n_pool0, n_pool1, &indices_out[f], &freq_out[f], &k_out[f]);
             });
-        } catch (...) {
-            for (int32_t f = 0; f < n_files; ++f) { std::free(indices_out[f]); std::free(freq_out[f]); indices_out[f] = nullptr; freq_out[f] = nullptr; k_out[f] = 0; }
-            throw;
-        }
+        });
     });
 }
 
@@ -703,17 +672,112 @@ int scg_count_dual_barcodes_files(const char* const* paths1, const char* constan
         for (int32_t f = 0; f < n_files; ++f) if (!paths1[f] || !paths2[f]) throw Error(SCG_ERR_INVALID, "null argument");
         if (n_files == 0) return;
         { scg::FastqStream probe1(paths1[0]); scg::FastqStream probe2(paths2[0]); }
-        std::vector<int> devices = device_list();
-        if (devices.size() > static_cast<size_t>(n_files)) devices.resize(static_cast<size_t>(n_files));
+        const std::vector<int> devices = devices_for_files(n_files);
         PlanSet set(compile_dual(constant1, reverse1, mismatches1, pool1, constant2, reverse2, mismatches2, pool2, n_pool, randomized, use_first), devices);
         const size_t stride = static_cast<size_t>(n_pool);
-        schedule_files(n_files, set, [&](scg_plan* P, int32_t f) {
-            scg::FastqStream fq1(paths1[f]);
-            scg::FastqStream fq2(paths2[f]);
-            reset_plan(P);
-            count_paired_files(P, paths1[f], paths2[f], fq1, fq2, nthreads);
+        schedule_paired(n_files, set, paths1, paths2, nthreads, [&](scg_plan* P, int32_t f) {
             read_counters(P, counts_out + stride * static_cast<size_t>(f));
             totals_out[f] = narrow_total(P->total);
+        });
+    });
+}
+
+// The four entries below check their arguments -- the template and the pools are compiled, host work only -- before any
+// file is opened and any device is touched; then every device gets its plan and takes the files one at a time.  A plan
+// starts every file from reset_plan (counters, sparse combinations, runs in flight, the oversize-read flag), and a file's
+// outputs are read by the function its one-file entry reads them with (result_counts, result_diagnostics).
+
+int scg_count_dual_barcodes_diagnostics_files(const char* const* paths1, const char* constant1, int reverse1, int mismatches1, const char* const* pool1,
+                                              const char* const* paths2, const char* constant2, int reverse2, int mismatches2, const char* const* pool2,
+                                              int32_t n_pool, int32_t n_files, int randomized, int use_first, int nthreads,
+                                              int32_t* counts_out, int32_t** invalid_indices_out, int32_t** invalid_freq_out, int64_t* k_out,
+                                              int32_t* totals_out, int32_t* barcode1_only_out, int32_t* barcode2_only_out,
+                                              char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (n_files < 0 || (n_files > 0 && (!paths1 || !paths2 || !invalid_indices_out || !invalid_freq_out || !k_out || !totals_out ||
+                                            !barcode1_only_out || !barcode2_only_out || (n_pool > 0 && !counts_out)))) {
+            throw Error(SCG_ERR_INVALID, "null argument");
+        }
+        with_per_file_outputs(invalid_indices_out, invalid_freq_out, k_out, n_files, [&] {
+            for (int32_t f = 0; f < n_files; ++f) if (!paths1[f] || !paths2[f]) throw Error(SCG_ERR_INVALID, "null argument");
+            if (n_files == 0) return;
+            auto compiled = compile_dual(constant1, reverse1, mismatches1, pool1, constant2, reverse2, mismatches2, pool2, n_pool, randomized, use_first, 1);
+            PlanSet set(std::move(compiled), devices_for_files(n_files));
+            const size_t stride = static_cast<size_t>(n_pool);
+            schedule_paired(n_files, set, paths1, paths2, nthreads, [&](scg_plan* P, int32_t f) {
+                result_diagnostics(std::vector<scg_plan*>(1, P), counts_out + stride * static_cast<size_t>(f), &invalid_indices_out[f], &invalid_freq_out[f],
+                                   &k_out[f], &totals_out[f], &barcode1_only_out[f], &barcode2_only_out[f]);
+            });
+        });
+    });
+}
+
+int scg_count_dual_barcodes_single_end_files(const char* const* paths, int32_t n_files, const char* constant,
+                                             const char* const* const* pools, const int32_t* n_pools, int32_t n_regions,
+                                             int strand, int mismatches, int use_first, int nthreads,
+                                             int32_t* counts_out, int32_t* totals_out, char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (n_files < 0 || (n_files > 0 && (!paths || !totals_out || (n_regions > 0 && n_pools && n_pools[0] > 0 && !counts_out)))) {
+            throw Error(SCG_ERR_INVALID, "null argument");
+        }
+        for (int32_t f = 0; f < n_files; ++f) if (!paths[f]) throw Error(SCG_ERR_INVALID, "null argument");
+        if (n_files == 0) return;
+        auto compiled = compile_dual_single_end(constant, strand, pools, n_pools, n_regions, mismatches, use_first);
+        PlanSet set(std::move(compiled), devices_for_files(n_files));
+        const size_t stride = static_cast<size_t>(set.first()->n_pool[0]);
+        schedule_single_end(n_files, set, paths, nthreads, [&](scg_plan* P, int32_t f) {
+            result_counts(std::vector<scg_plan*>(1, P), counts_out + stride * static_cast<size_t>(f), &totals_out[f]);
+        });
+    });
+}
+
+int scg_count_dual_barcodes_single_end_diagnostics_files(const char* const* paths, int32_t n_files, const char* constant,
+                                                         const char* const* const* pools, const int32_t* n_pools, int32_t n_regions,
+                                                         int strand, int mismatches, int use_first, int nthreads,
+                                                         int32_t* counts_out, int32_t** invalid_indices_out, int32_t** invalid_freq_out, int64_t* k_out,
+                                                         int32_t* totals_out, char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (n_files < 0 || (n_files > 0 && (!paths || !invalid_indices_out || !invalid_freq_out || !k_out || !totals_out ||
+                                            (n_regions > 0 && n_pools && n_pools[0] > 0 && !counts_out)))) {
+            throw Error(SCG_ERR_INVALID, "null argument");
+        }
+        with_per_file_outputs(invalid_indices_out, invalid_freq_out, k_out, n_files, [&] {
+            for (int32_t f = 0; f < n_files; ++f) if (!paths[f]) throw Error(SCG_ERR_INVALID, "null argument");
+            if (n_files == 0) return;
+            auto compiled = compile_dual_single_end_diag(constant, strand, pools, n_pools, n_regions, mismatches, use_first);
+            PlanSet set(std::move(compiled), devices_for_files(n_files));
+            const size_t stride = static_cast<size_t>(set.first()->n_pool[0]);
+            schedule_single_end(n_files, set, paths, nthreads, [&](scg_plan* P, int32_t f) {
+                result_diagnostics(std::vector<scg_plan*>(1, P), counts_out + stride * static_cast<size_t>(f), &invalid_indices_out[f], &invalid_freq_out[f],
+                                   &k_out[f], &totals_out[f], nullptr, nullptr);
+            });
+        });
+    });
+}
+
+int scg_count_combo_barcodes_paired_files(const char* const* paths1, const char* constant1, int reverse1, int mismatches1,
+                                          const char* const* pool1, int32_t n_pool1,
+                                          const char* const* paths2, const char* constant2, int reverse2, int mismatches2,
+                                          const char* const* pool2, int32_t n_pool2, int32_t n_files,
+                                          int randomized, int use_first, int nthreads,
+                                          int32_t** indices_out, int32_t** freq_out, int64_t* k_out,
+                                          int32_t* totals_out, int32_t* barcode1_only_out, int32_t* barcode2_only_out,
+                                          char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (n_files < 0 || (n_files > 0 && (!paths1 || !paths2 || !indices_out || !freq_out || !k_out || !totals_out ||
+                                            !barcode1_only_out || !barcode2_only_out))) {
+            throw Error(SCG_ERR_INVALID, "null argument");
+        }
+        with_per_file_outputs(indices_out, freq_out, k_out, n_files, [&] {
+            for (int32_t f = 0; f < n_files; ++f) if (!paths1[f] || !paths2[f]) throw Error(SCG_ERR_INVALID, "null argument");
+            if (n_files == 0) return;
+            auto compiled = compile_paired_combo(constant1, reverse1, mismatches1, pool1, n_pool1, constant2, reverse2, mismatches2, pool2, n_pool2,
+                                                 randomized, use_first);
+            PlanSet set(std::move(compiled), devices_for_files(n_files));
+            schedule_paired(n_files, set, paths1, paths2, nthreads, [&](scg_plan* P, int32_t f) {
+                result_diagnostics(std::vector<scg_plan*>(1, P), nullptr, &indices_out[f], &freq_out[f], &k_out[f], &totals_out[f],
+                                   &barcode1_only_out[f], &barcode2_only_out[f]);
+            });
         });
     });
 }

@@ -498,10 +498,27 @@ uint64_t text_bytes_hint(const char* path);
 void set_thread_devices(const int* devices, int32_t n);      // scg_set_devices()
 std::unique_ptr<scg_plan> clone_compiled(const scg_plan& a);
 void schedule_files(int32_t n_files, const PlanSet& set, const std::function<void(scg_plan*, int32_t)>& per_file);
+std::vector<int> devices_for_files(int32_t n_files);
+void schedule_single_end(int32_t n_files, const PlanSet& set, const char* const* paths, int nthreads, const std::function<void(scg_plan*, int32_t)>& read_file);
+void schedule_paired(int32_t n_files, const PlanSet& set, const char* const* paths1, const char* const* paths2, int nthreads,
+                     const std::function<void(scg_plan*, int32_t)>& read_file);
 void combo_compact(const int32_t* cells, int32_t n0, int32_t n1, int32_t** indices_out, int32_t** freq_out, int64_t* k_out);
 void combos_from_sparse(const std::unordered_map<uint64_t, int64_t>& m, int32_t** indices_out, int32_t** freq_out, int64_t* k_out);
 void diagnostics_from_counters(const scg_plan* P, const std::vector<int32_t>& all, int32_t* counts_out, int32_t** idx_out, int32_t** freq_out, int64_t* k_out,
                                int32_t* b1, int32_t* b2, const std::unordered_map<uint64_t, int64_t>* sparse = nullptr);
+// One counted input -> the outputs of its entry point.  `plans`: the plans that counted it -- one per device of a one-file
+// entry (their counters are summed, their combinations merged), the worker's own plan in a many-files entry.
+void read_plans(const std::vector<scg_plan*>& plans, int32_t* counts_out);
+int64_t total_of(const std::vector<scg_plan*>& plans);
+std::unordered_map<uint64_t, int64_t> sparse_merged(const std::vector<scg_plan*>& plans);
+void result_counts(const std::vector<scg_plan*>& plans, int32_t* counts_out, int32_t* total_out);
+// (diagnostics plans of every kind: include.invalid=TRUE, paired and single-end, and the paired combinations, which have
+// no counts_out; b1_out / b2_out may be null)
+void result_diagnostics(const std::vector<scg_plan*>& plans, int32_t* counts_out, int32_t** idx_out, int32_t** freq_out, int64_t* k_out,
+                        int32_t* total_out, int32_t* b1_out, int32_t* b2_out);
+// The per-file malloc'd outputs of a many-files entry (caller-allocated arrays of n_files entries): all-NULL before `body`
+// runs, and again -- everything released -- when it throws, so that the caller never has to guess what to free.
+void with_per_file_outputs(int32_t** idx_out, int32_t** freq_out, int64_t* k_out, int32_t n_files, const std::function<void()>& body);
 
 } // namespace scgapi
 

@@ -8,6 +8,7 @@ void reset_plan(scg_plan* P) {
     DeviceGuard g(P->device);
     if (P->n_counters) HIP_CHECK(hipMemset(P->counters, 0, static_cast<size_t>(P->n_counters) * sizeof(int32_t)));
     if (P->replica_shift > 0) HIP_CHECK(hipMemset(P->replicas.p, 0, P->replicas.bytes));
+    HIP_CHECK(hipMemset(P->error_flag.p, 0, sizeof(int32_t)));    // (what set it is recounted, or belongs to the previous file)
     HIP_CHECK(hipStreamSynchronize(nullptr));               // (the fills are only enqueued: scg_plan::upload)
     for (auto& kv : P->pair_stream) {                       // (sparse mode: batches in flight are let finish and dropped)
         if (kv.second.pending) { HIP_CHECK(hipEventSynchronize(kv.second.done)); kv.second.pending = 0; }
@@ -155,6 +156,32 @@ void schedule_files(int32_t n_files, const PlanSet& set, const std::function<voi
     if (bad < n_files) throw Error(bad_code, bad_msg);
 }
 
+// What the many-files entries share: at most one device per file; and per file of a worker's plan: the readers, a full
+// reset of the plan, the file's ladder, then `read_file(plan, f)` stores file f's outputs.
+std::vector<int> devices_for_files(int32_t n_files) {
+    std::vector<int> devices = device_list();
+    if (devices.size() > static_cast<size_t>(n_files)) devices.resize(static_cast<size_t>(n_files));
+    return devices;
+}
+void schedule_single_end(int32_t n_files, const PlanSet& set, const char* const* paths, int nthreads, const std::function<void(scg_plan*, int32_t)>& read_file) {
+    schedule_files(n_files, set, [&](scg_plan* P, int32_t f) {
+        scg::FastqStream fq(paths[f]);
+        reset_plan(P);
+        count_single_end(std::vector<scg_plan*>(1, P), paths[f], fq, nthreads);
+        read_file(P, f);
+    });
+}
+void schedule_paired(int32_t n_files, const PlanSet& set, const char* const* paths1, const char* const* paths2, int nthreads,
+                     const std::function<void(scg_plan*, int32_t)>& read_file) {
+    schedule_files(n_files, set, [&](scg_plan* P, int32_t f) {
+        scg::FastqStream fq1(paths1[f]);
+        scg::FastqStream fq2(paths2[f]);
+        reset_plan(P);
+        count_paired_files(P, paths1[f], paths2[f], fq1, fq2, nthreads);
+        read_file(P, f);
+    });
+}
+
 void combo_compact(const int32_t* cells, int32_t n0, int32_t n1, int32_t** indices_out, int32_t** freq_out, int64_t* k_out) {
     int64_t total = static_cast<int64_t>(n0) * n1, k = 0;
     for (int64_t c = 0; c < total; ++c) k += cells[c] != 0;
@@ -248,23 +275,30 @@ std::vector<scg_plan*> PlanSet::all() const {
     for (auto& p : plans) v.push_back(p.get());
     return v;
 }
-int64_t PlanSet::total() const {
+int64_t PlanSet::total() const { return total_of(all()); }
+void PlanSet::read(int32_t* counts_out) const { read_plans(all(), counts_out); }
+void PlanSet::reset() const { for (auto& p : plans) reset_plan(p.get()); }
+std::unordered_map<uint64_t, int64_t> PlanSet::sparse_merged() const { return scgapi::sparse_merged(all()); }
+
+// ---- one counted input -> the outputs of its entry point ------------------------------------------------------
+int64_t total_of(const std::vector<scg_plan*>& plans) {
     int64_t t = 0;
-    for (auto& p : plans) t += p->total;
+    for (scg_plan* p : plans) t += p->total;
     return t;
 }
-void PlanSet::read(int32_t* counts_out) const {
+
+void read_plans(const std::vector<scg_plan*>& plans, int32_t* counts_out) {
     if (plans.size() == 1) {
         DeviceGuard g(plans[0]->device);
-        read_counters(plans[0].get(), counts_out);
+        read_counters(plans[0], counts_out);
         return;
     }
     const size_t n = static_cast<size_t>(plans[0]->n_counters);
     std::vector<int64_t> acc(n, 0);
     std::vector<int32_t> part(n + 1);
-    for (auto& p : plans) {
+    for (scg_plan* p : plans) {
         DeviceGuard g(p->device);
-        read_counters(p.get(), part.data());
+        read_counters(p, part.data());
         for (size_t i = 0; i < n; ++i) acc[i] += part[i];
     }
     if (counts_out) {
@@ -274,15 +308,46 @@ void PlanSet::read(int32_t* counts_out) const {
         }
     }
 }
-void PlanSet::reset() const { for (auto& p : plans) reset_plan(p.get()); }
-std::unordered_map<uint64_t, int64_t> PlanSet::sparse_merged() const {
+
+std::unordered_map<uint64_t, int64_t> sparse_merged(const std::vector<scg_plan*>& plans) {
     std::unordered_map<uint64_t, int64_t> all;
-    for (auto& p : plans) {
-        retire_all_pairs(p.get());
+    for (scg_plan* p : plans) {
+        retire_all_pairs(p);
         if (all.empty()) all = p->sparse_counts;
         else for (auto& kv : p->sparse_counts) all[kv.first] += kv.second;
     }
     return all;
+}
+
+void result_counts(const std::vector<scg_plan*>& plans, int32_t* counts_out, int32_t* total_out) {
+    read_plans(plans, counts_out);
+    *total_out = narrow_total(total_of(plans));
+}
+
+void result_diagnostics(const std::vector<scg_plan*>& plans, int32_t* counts_out, int32_t** idx_out, int32_t** freq_out, int64_t* k_out,
+                        int32_t* total_out, int32_t* b1_out, int32_t* b2_out) {
+    const scg_plan* P = plans[0];
+    std::vector<int32_t> all(static_cast<size_t>(P->n_counters) + 1);
+    read_plans(plans, all.data());
+    const int32_t total = narrow_total(total_of(plans));       // (before anything is allocated for the caller)
+    int32_t b1 = 0, b2 = 0;
+    const auto sparse = P->sparse ? sparse_merged(plans) : std::unordered_map<uint64_t, int64_t>();
+    diagnostics_from_counters(P, all, counts_out, idx_out, freq_out, k_out, b1_out ? b1_out : &b1, b2_out ? b2_out : &b2,
+                              P->sparse ? &sparse : nullptr);
+    *total_out = total;
+}
+
+void with_per_file_outputs(int32_t** idx_out, int32_t** freq_out, int64_t* k_out, int32_t n_files, const std::function<void()>& body) {
+    for (int32_t f = 0; f < n_files; ++f) { idx_out[f] = nullptr; freq_out[f] = nullptr; k_out[f] = 0; }
+    try {
+        body();
+    } catch (...) {
+        for (int32_t f = 0; f < n_files; ++f) {
+            std::free(idx_out[f]); std::free(freq_out[f]);
+            idx_out[f] = nullptr; freq_out[f] = nullptr; k_out[f] = 0;
+        }
+        throw;
+    }
 }
 
 void set_thread_devices(const int* devices, int32_t n) { tl_devices.assign(devices, devices + n); }

@@ -158,12 +158,34 @@ Rcpp::List match_barcodes(Rcpp::CharacterVector sequences, Rcpp::CharacterVector
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Many files in one native call: optional additions for the matrixOf* functions.  With these three exported, e.g.
+// Many files in one native call: optional additions for the matrixOf* functions.  With these seven exported, e.g.
 // matrixOfSingleBarcodes (R/countSingleBarcodes.R:112-126) replaces its
 //     out <- bplapply(files, FUN=countSingleBarcodes, ..., BPPARAM=BPPARAM)
 // by one call whose result it unpacks into the same per-file list; libscg schedules the files over the GPUs itself
-// (one file at a time per device, library compiled once), so no BiocParallel worker processes are needed.
+// (one file at a time per device, library compiled once), so no BiocParallel worker processes are needed.  The same
+// goes for matrixOfDualBarcodes (with and without include.invalid), matrixOfDualBarcodesSingleEnd (likewise) and
+// matrixOfPairedComboBarcodes: INTEGRATION.md lists which wrapper reaches which export.
 // ---------------------------------------------------------------------------------------------------------------
+
+namespace {
+// The per-file malloc'd outputs of a many-files entry: file f's 2 x K_f matrix of indices and its K_f frequencies.  All of
+// them are released when this goes out of scope, also when an allocation on the R side throws half-way through the files.
+struct PerFileCombinations {
+    std::vector<int32_t*> idx, freq;
+    std::vector<int64_t> k;
+    explicit PerFileCombinations(size_t n_files) : idx(n_files, nullptr), freq(n_files, nullptr), k(n_files, 0) {}
+    PerFileCombinations(const PerFileCombinations&) = delete;
+    PerFileCombinations& operator=(const PerFileCombinations&) = delete;
+    ~PerFileCombinations() { for (size_t f = 0; f < idx.size(); ++f) { scg_free(idx[f]); scg_free(freq[f]); } }
+    Rcpp::IntegerMatrix indices(R_xlen_t f) const {
+        Rcpp::IntegerMatrix m(2, k[f]);
+        std::copy(idx[f], idx[f] + 2 * k[f], m.begin());
+        return m;
+    }
+    Rcpp::IntegerVector counts(R_xlen_t f) const { return Rcpp::IntegerVector(freq[f], freq[f] + k[f]); }
+    Rcpp::List both(R_xlen_t f) const { return Rcpp::List::create(indices(f), counts(f)); }
+};
+}
 
 //[[Rcpp::export(rng=false)]]
 Rcpp::List count_single_barcodes_files(Rcpp::CharacterVector paths, std::string constant, int strand, Rcpp::CharacterVector pool,
@@ -183,20 +205,15 @@ Rcpp::List count_combo_barcodes_single_files(Rcpp::CharacterVector paths, std::s
     if (pool.size() != 2) Rcpp::stop("currently expecting only 2 variable regions for single-end combinatorial barcodes");
     Rcpp::CharacterVector c0(pool[0]), c1(pool[1]);
     auto f = borrow(paths), p0 = borrow(c0), p1 = borrow(c1);
-    std::vector<int32_t*> idx(f.size(), nullptr), freq(f.size(), nullptr);
-    std::vector<int64_t> k(f.size(), 0);
+    PerFileCombinations found(f.size());
     Rcpp::IntegerVector totals(paths.size());
     char err[1024];
     check(scg_count_combo_barcodes_single_files(f.data(), (int32_t)f.size(), constant.c_str(), strand, p0.data(), (int32_t)p0.size(),
                                                 p1.data(), (int32_t)p1.size(), mismatches, use_first, nthreads,
-                                                idx.data(), freq.data(), k.data(), totals.begin(), err, sizeof(err)), err);
+                                                found.idx.data(), found.freq.data(), found.k.data(), totals.begin(), err, sizeof(err)), err);
     Rcpp::List out(paths.size());                        // one count_combo_barcodes_single() result per file
     for (R_xlen_t i = 0; i < paths.size(); ++i) {
-        Rcpp::IntegerMatrix indices(2, k[i]);
-        std::copy(idx[i], idx[i] + 2 * k[i], indices.begin());
-        Rcpp::IntegerVector counts(freq[i], freq[i] + k[i]);
-        scg_free(idx[i]); scg_free(freq[i]);
-        out[i] = Rcpp::List::create(indices, counts, Rcpp::IntegerVector::create(totals[i]));
+        out[i] = Rcpp::List::create(found.indices(i), found.counts(i), Rcpp::IntegerVector::create(totals[i]));
     }
     return out;
 }
@@ -215,4 +232,102 @@ Rcpp::List count_dual_barcodes_files(Rcpp::CharacterVector paths1, std::string c
                                         f2.data(), constant2.c_str(), reverse2, mismatches2, p2.data(), (int32_t)p1.size(), (int32_t)f1.size(),
                                         randomized, use_first, nthreads, counts.begin(), totals.begin(), err, sizeof(err)), err);
     return Rcpp::List::create(counts, totals);
+}
+
+namespace {
+// A list of pools (one per variable region) as the rows libscg takes.
+struct PoolRows {
+    std::vector<std::vector<const char*> > cols;
+    std::vector<const char* const*> rows;
+    std::vector<int32_t> sizes;
+    explicit PoolRows(const Rcpp::List& pools) {
+        for (R_xlen_t p = 0; p < pools.size(); ++p) {
+            cols.push_back(borrow(Rcpp::CharacterVector(pools[p])));
+            sizes.push_back((int32_t)cols.back().size());
+        }
+        for (auto& c : cols) rows.push_back(c.data());
+    }
+};
+}
+
+// matrixOfDualBarcodes(include.invalid=TRUE): List(counts matrix, per-file List(indices, frequencies), totals,
+// barcode-1-only, barcode-2-only) -- per file what count_dual_barcodes(diagnostics=TRUE) returns.
+//[[Rcpp::export(rng=false)]]
+Rcpp::List count_dual_barcodes_diagnostics_files(Rcpp::CharacterVector paths1, std::string constant1, bool reverse1, int mismatches1,
+                                                 Rcpp::CharacterVector pool1,
+                                                 Rcpp::CharacterVector paths2, std::string constant2, bool reverse2, int mismatches2,
+                                                 Rcpp::CharacterVector pool2, bool randomized, bool use_first, int nthreads) {
+    if (pool1.size() != pool2.size()) Rcpp::stop("both barcode pools should be of the same length");
+    if (paths1.size() != paths2.size()) Rcpp::stop("'paths1' and 'paths2' should be of the same length");
+    auto f1 = borrow(paths1), f2 = borrow(paths2), p1 = borrow(pool1), p2 = borrow(pool2);
+    PerFileCombinations found(f1.size());
+    Rcpp::IntegerMatrix counts((int)pool1.size(), paths1.size());
+    Rcpp::IntegerVector totals(paths1.size()), b1(paths1.size()), b2(paths1.size());
+    char err[1024];
+    check(scg_count_dual_barcodes_diagnostics_files(f1.data(), constant1.c_str(), reverse1, mismatches1, p1.data(),
+                                                    f2.data(), constant2.c_str(), reverse2, mismatches2, p2.data(), (int32_t)p1.size(),
+                                                    (int32_t)f1.size(), randomized, use_first, nthreads, counts.begin(),
+                                                    found.idx.data(), found.freq.data(), found.k.data(), totals.begin(), b1.begin(), b2.begin(),
+                                                    err, sizeof(err)), err);
+    Rcpp::List invalid(paths1.size());
+    for (R_xlen_t i = 0; i < paths1.size(); ++i) invalid[i] = found.both(i);
+    return Rcpp::List::create(counts, invalid, totals, b1, b2);
+}
+
+// matrixOfDualBarcodesSingleEnd: List(counts matrix, totals).
+//[[Rcpp::export(rng=false)]]
+Rcpp::List count_dual_barcodes_single_end_files(Rcpp::CharacterVector paths, std::string constant, Rcpp::List pools, int strand,
+                                                int mismatches, bool use_first, int nthreads) {
+    auto f = borrow(paths);
+    PoolRows p(pools);
+    Rcpp::IntegerMatrix counts(p.sizes.empty() ? 0 : p.sizes[0], paths.size());
+    Rcpp::IntegerVector totals(paths.size());
+    char err[1024];
+    check(scg_count_dual_barcodes_single_end_files(f.data(), (int32_t)f.size(), constant.c_str(), p.rows.data(), p.sizes.data(),
+                                                   (int32_t)p.rows.size(), strand, mismatches, use_first, nthreads,
+                                                   counts.begin(), totals.begin(), err, sizeof(err)), err);
+    return Rcpp::List::create(counts, totals);
+}
+
+// matrixOfDualBarcodesSingleEnd(include.invalid=TRUE): List(counts matrix, per-file List(indices, frequencies), totals).
+//[[Rcpp::export(rng=false)]]
+Rcpp::List count_dual_barcodes_single_end_diagnostics_files(Rcpp::CharacterVector paths, std::string constant, Rcpp::List pools, int strand,
+                                                            int mismatches, bool use_first, int nthreads) {
+    auto f = borrow(paths);
+    PoolRows p(pools);
+    PerFileCombinations found(f.size());
+    Rcpp::IntegerMatrix counts(p.sizes.empty() ? 0 : p.sizes[0], paths.size());
+    Rcpp::IntegerVector totals(paths.size());
+    char err[1024];
+    check(scg_count_dual_barcodes_single_end_diagnostics_files(f.data(), (int32_t)f.size(), constant.c_str(), p.rows.data(), p.sizes.data(),
+                                                               (int32_t)p.rows.size(), strand, mismatches, use_first, nthreads,
+                                                               counts.begin(), found.idx.data(), found.freq.data(), found.k.data(), totals.begin(),
+                                                               err, sizeof(err)), err);
+    Rcpp::List invalid(paths.size());
+    for (R_xlen_t i = 0; i < paths.size(); ++i) invalid[i] = found.both(i);
+    return Rcpp::List::create(counts, invalid, totals);
+}
+
+// matrixOfPairedComboBarcodes: one count_combo_barcodes_paired() result per pair of files.
+//[[Rcpp::export(rng=false)]]
+Rcpp::List count_combo_barcodes_paired_files(Rcpp::CharacterVector paths1, std::string constant1, bool reverse1, int mismatches1,
+                                             Rcpp::CharacterVector pool1,
+                                             Rcpp::CharacterVector paths2, std::string constant2, bool reverse2, int mismatches2,
+                                             Rcpp::CharacterVector pool2, bool randomized, bool use_first, int nthreads) {
+    if (paths1.size() != paths2.size()) Rcpp::stop("'paths1' and 'paths2' should be of the same length");
+    auto f1 = borrow(paths1), f2 = borrow(paths2), p1 = borrow(pool1), p2 = borrow(pool2);
+    PerFileCombinations found(f1.size());
+    Rcpp::IntegerVector totals(paths1.size()), b1(paths1.size()), b2(paths1.size());
+    char err[1024];
+    check(scg_count_combo_barcodes_paired_files(f1.data(), constant1.c_str(), reverse1, mismatches1, p1.data(), (int32_t)p1.size(),
+                                                f2.data(), constant2.c_str(), reverse2, mismatches2, p2.data(), (int32_t)p2.size(),
+                                                (int32_t)f1.size(), randomized, use_first, nthreads,
+                                                found.idx.data(), found.freq.data(), found.k.data(), totals.begin(), b1.begin(), b2.begin(),
+                                                err, sizeof(err)), err);
+    Rcpp::List out(paths1.size());
+    for (R_xlen_t i = 0; i < paths1.size(); ++i) {
+        out[i] = Rcpp::List::create(found.indices(i), found.counts(i), Rcpp::IntegerVector::create(totals[i]),
+                                    Rcpp::IntegerVector::create(b1[i]), Rcpp::IntegerVector::create(b2[i]));
+    }
+    return out;
 }
