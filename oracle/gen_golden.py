@@ -20,6 +20,10 @@ produced for them.  Two files:
 
     python oracle/gen_golden.py            (everything)
     python oracle/gen_golden.py configs    (only config_scale_kaori.json)
+    python oracle/gen_golden.py crowded    (only kaori_crowded.json)
+
+  tests/golden/kaori_crowded.json  -- kaori's outputs (one thread) on the crowded match, single and combo cases of tests/gen.py
+        (crowded_golden_cases: star-and-ladder pools, budgets up to 5), by name, each with a digest of its seeded inputs.
 """
 from __future__ import annotations
 
@@ -354,9 +358,27 @@ def big_cases(ref: KaoriRef, tmp: str) -> None:
     print(f"large grid: {len(done['expect']['freq'])} combinations of {done['expect']['total']} reads")
 
 
+def crowded_cases(ref: KaoriRef, tmp: str) -> None:
+    """tests/golden/kaori_crowded.json: inputs by seed (tests/gen.py::crowded_golden_cases) + digest, outputs in full."""
+    out = {}
+    for name, build in gen.crowded_golden_cases().items():
+        case = build()
+        done = run_case(ref, case, tmp)
+        assert "error" not in done["expect"], (name, done["expect"])
+        out[name] = {"inputs_sha256": gen.case_digest(case), "expect": done["expect"]}
+    with open(os.path.join(OUT, "kaori_crowded.json"), "w") as f:
+        json.dump({"generator": "oracle/gen_golden.py::crowded_cases", "reference": "kaori v1.1.1 (screenCounter 1.5.1)",
+                   "inputs": "tests/gen.py::crowded_golden_cases()", "seed": gen.CROWDED_SEED, "cases": out}, f, separators=(",", ":"))
+    print(f"crowded pools: {len(out)} cases")
+
+
 def main() -> None:
     ref = KaoriRef()
     os.makedirs(OUT, exist_ok=True)
+    if sys.argv[1:] == ["crowded"]:                 # only tests/golden/kaori_crowded.json
+        with tempfile.TemporaryDirectory() as tmp:
+            crowded_cases(ref, tmp)
+        return
     if sys.argv[1:] == ["big"]:                     # only the round-3 files (the others stay byte for byte)
         with tempfile.TemporaryDirectory() as tmp:
             big_cases(ref, tmp)
@@ -368,6 +390,7 @@ def main() -> None:
     with tempfile.TemporaryDirectory() as tmp:
         config_scale_fixture(ref, tmp)
         big_cases(ref, tmp)
+        crowded_cases(ref, tmp)
         ka = [run_case(ref, c, tmp) for c in known_answers()]
         for c in ka:
             check_r_expect(c)

@@ -485,3 +485,459 @@ def split_pair(fill: Filler, construct: str, k: int, n1: int, n2: int) -> tuple[
     """Two neighbouring reads: the first (n1 bases) ends with the construct's first k bases, the second (n2 bases)
     starts with the rest."""
     return fill(n1 - k) + construct[:k], construct[k:] + fill(n2 - (len(construct) - k))
+
+
+# ---------------------------------------------------------------------------------------------
+# Crowded pools: "star and ladder" libraries whose entries sit one or two substitutions apart, at the positions where the
+# index's position groups begin and end, and queries built for a known outcome (tests/test_crowded_cpu.py checks the
+# outcomes with a brute force; tests/test_gpu_crowded.py runs them through every matcher path).
+# ---------------------------------------------------------------------------------------------
+IUPAC_SETS = {"A": "A", "C": "C", "G": "G", "T": "T", "R": "AG", "Y": "CT", "S": "CG", "W": "AT", "K": "GT", "M": "AC",
+              "B": "CGT", "D": "AGT", "H": "ACT", "V": "ACG", "N": "ACGT"}
+_ONE_HOT = {"A": 1, "C": 2, "G": 4, "T": 8}
+_SET_BITS = {c: sum(_ONE_HOT[b] for b in s) for c, s in IUPAC_SETS.items()}
+CROWDED_SHORT = 16      # below this length a pool stays inside {A, C, G}: see crowded_pool
+
+
+def crowded_positions(length: int) -> list[int]:
+    """Both ends, both sides of every half and quarter slice edge of the index builders (floor(k * length / parts)), and both
+    sides of the 32-, 64-, 128- and 192-bit word edges of the key planes."""
+    want = {0, length - 1, 31, 32, 63, 64, 127, 128, 191, 192}
+    for parts in (2, 4):
+        for k in range(parts + 1):
+            want.update((k * length // parts - 1, k * length // parts))
+    return sorted(p for p in want if 0 <= p < length)
+
+
+def position_groups(length: int, budget: int) -> list[frozenset]:
+    """The position groups of an index built for `budget` (finish_index, finish_index_n): the whole key, its halves, the six
+    pairs of quarters, the quarters; none for wider budgets (dense scans)."""
+    def part(i, parts):
+        return frozenset(range(i * length // parts, (i + 1) * length // parts))
+    if budget == 0:
+        return [part(0, 1)]
+    if budget == 1:
+        return [part(0, 2), part(1, 2)]
+    if budget == 2:
+        return [part(a, 4) | part(b, 4) for a, b in ((0, 1), (2, 3), (0, 2), (1, 3), (0, 3), (1, 2))]
+    if budget == 3:
+        return [part(q, 4) for q in range(4)]
+    return []
+
+
+def _quarter(length: int, p: int) -> int:
+    return next(q for q in range(4) if q * length // 4 <= p < (q + 1) * length // 4)
+
+
+def _bits(s: str, table: dict) -> int:
+    """4 bits per position: the bases a library string allows (_SET_BITS), or the one base a query holds (_ONE_HOT; none for
+    any other byte).  The Hamming distance is then length - popcount(entry & query)."""
+    v = 0
+    for i, c in enumerate(s.upper()):
+        v |= table.get(c, 0) << (4 * i)
+    return v
+
+
+def crowded_outcome(pool_bits: list[int], query: str, cap: int):
+    """("hit", distance, index) for a unique minimum within cap, ("tie", distance, indices), or ("miss", minimum, None)."""
+    q = _bits(query, _ONE_HOT)
+    dist = [len(query) - (e & q).bit_count() for e in pool_bits]
+    best = min(dist)
+    if best > cap:
+        return "miss", best, None
+    who = [i for i, d in enumerate(dist) if d == best]
+    return ("hit", best, who[0]) if len(who) == 1 else ("tie", best, who)
+
+
+class CrowdedPool(list):
+    """The library strings, with what they were built from: `stars` = [(centre, {position: substituted base}, {position:
+    bases that some entry of the star allows there})], one per centre; `positions` = crowded_positions(length); `alphabet`
+    of the centres."""
+    stars: list
+    positions: list
+    alphabet: str
+
+
+def crowded_pool(rng: random.Random, length: int, budget: int, centres: int = 6, arms: int = None, doubles: int = 3,
+                 iupac: bool = None, alphabet: str = None, min_dist: int = None) -> CrowdedPool:
+    """A library of `centres` stars: per centre, the centre with one base substituted at p for (up to `arms` of) the positions
+    p of crowded_positions, `doubles` entries with two of those substitutions in different quarter slices (more for a wider
+    budget), and -- in about half the pools -- the centre itself.  In keys of up to 64 bases, two of a star's one-substitution
+    entries carry a two-base IUPAC code at p instead (the substituted base and another one, not the centre's), so that no two
+    entries share an expansion.
+
+    Below CROWDED_SHORT bases the pool stays inside {A, C, G}^length: in so small a space every query would otherwise lie
+    within a wide cap of some entry, and neither a miss beyond the cap nor a unique hit at a distance could be built; a
+    query's T then mismatches every entry.  `alphabet` and `min_dist` (between the centres) override that."""
+    if alphabet is None:
+        alphabet = "ACG" if length < CROWDED_SHORT else BASES
+    P = crowded_positions(length)
+    use = P if arms is None else sorted(rng.sample(P, min(arms, len(P))))
+    if iupac is None:
+        iupac = length <= 64
+    cs = make_pool(rng, centres, length, alphabet, min_dist=min(3, length) if min_dist is None else min_dist)
+    assert len(cs) == centres
+    keep_centre = rng.random() < 0.5
+    seen, out, stars = set(), CrowdedPool(), []
+
+    def add(s):
+        exp = [s]
+        for i, c in enumerate(s):
+            if c not in BASES:
+                exp = [e[:i] + b + e[i + 1:] for e in exp for b in IUPAC_SETS[c]]
+        if not seen.intersection(exp):
+            seen.update(exp)
+            out.append(s)
+
+    for c in cs:
+        alt = {p: rng.choice([b for b in alphabet if b != c[p]]) for p in use}
+        avoid = {p: c[p] + alt[p] for p in use}
+        arm = dict(alt)
+        if iupac:
+            for p in rng.sample(use, min(2, len(use))):
+                other = rng.choice([b for b in alphabet if b not in avoid[p]])
+                avoid[p] += other
+                arm[p] = next(k for k, v in IUPAC_SETS.items() if set(v) == {alt[p], other})
+        stars.append((c, alt, avoid))
+        if keep_centre:
+            add(c)
+        for p in use:
+            add(substitute(c, p, arm[p]))
+        made = 0
+        for _ in range(50):
+            if made >= doubles + max(budget - 2, 0) or len(use) < 2:
+                break
+            p, r = rng.sample(use, 2)
+            if _quarter(length, p) != _quarter(length, r):
+                add(substitute(substitute(c, p, alt[p]), r, alt[r]))
+                made += 1
+    order = list(out)
+    rng.shuffle(order)
+    out[:] = order
+    out.stars, out.positions, out.alphabet = stars, P, alphabet
+    return out
+
+
+def _third(rng, pool: CrowdedPool, star: int, p: int) -> str:
+    """a base at p that no entry of the star allows there; one outside the pool's alphabet where there is one"""
+    c, _, avoid = pool.stars[star]
+    free = [b for b in BASES if b not in avoid.get(p, c[p])]
+    return rng.choice([b for b in free if b not in pool.alphabet] or free)
+
+
+def _spread(rng, length: int, P: list, n: int, turn: int, fixed=()) -> list:
+    """n positions of P outside `fixed`, in as many different quarter slices as possible; `turn` rotates through the choices
+    of quarters so that every position group is in turn the only one left intact."""
+    import itertools
+    by_q = [[p for p in P if _quarter(length, p) == q and p not in fixed] for q in range(4)]
+    free = [q for q in range(4) if by_q[q] and q not in {_quarter(length, f) for f in fixed}]
+    picks = []
+    k = min(n, len(free))
+    if k:
+        combos = list(itertools.combinations(free, k))
+        for q in combos[turn % len(combos)]:
+            picks.append(rng.choice(by_q[q]))
+    rest = [p for p in P if p not in picks and p not in fixed]
+    rng.shuffle(rest)
+    picks += rest[:n - len(picks)]
+    if len(picks) < n:
+        others = [p for p in range(length) if p not in picks and p not in fixed and p not in P]
+        picks += rng.sample(others, n - len(picks))
+    return picks
+
+
+def crowded_query(rng, pool: CrowdedPool, kind: str, d: int, turn: int = 0, star: int = None):
+    """One query of the wanted kind against one star of the pool, or None where the key is too short for it:
+    "hit": a one-substitution entry with d further bases changed to third bases (distance d from it, d + 1 or more from the
+    rest of the star); "tie": the centre with the substitutions of two entries p and r and d - 1 third bases (distance d from
+    both); "centre": the centre with d third bases."""
+    length = len(pool[0])
+    star = rng.randrange(len(pool.stars)) if star is None else star
+    c, alt, _ = pool.stars[star]
+    arms = sorted(alt)
+    q = list(c)
+    if kind == "tie":
+        if len(arms) < 2 or d < 1 or d + 1 > length:
+            return None
+        by_q = {}
+        for p in arms:
+            by_q.setdefault(_quarter(length, p), []).append(p)
+        qs = sorted(by_q)
+        if len(qs) >= 2:
+            qa, qb = [(a, b) for a in qs for b in qs if a != b][turn % (len(qs) * (len(qs) - 1))]
+            p, r = rng.choice(by_q[qa]), rng.choice(by_q[qb])
+        else:
+            p, r = rng.sample(arms, 2)
+        q[p], q[r] = alt[p], alt[r]
+        for s in _spread(rng, length, pool.positions, d - 1, turn // 12, fixed=(p, r)):
+            q[s] = _third(rng, pool, star, s)
+    else:
+        fixed = ()
+        if kind == "hit":
+            mine = [p for p in arms if _quarter(length, p) == turn % 4] or arms
+            p = rng.choice(mine)
+            q[p] = alt[p]
+            fixed = (p,)
+        if d + len(fixed) > length:
+            return None
+        for s in _spread(rng, length, pool.positions, d, turn // 4, fixed=fixed):
+            q[s] = _third(rng, pool, star, s)
+    return "".join(q)
+
+
+def crowded_queries(rng: random.Random, pool: CrowdedPool, budget: int, n: int = 240, annotate: bool = False) -> list:
+    """n queries for a cap of `budget`, each built for its outcome and kept only if a Hamming count confirms it: 36 % ties
+    between two entries at each distance 1..budget, 36 % unique hits at each distance 1..budget, 16 % misses one substitution
+    beyond the cap, the rest exact hits; the mismatches sit on crowded_positions and rotate through the quarter slices.  One
+    query in eight then gets a byte that is no base at a random or a crowded position (whatever that makes of it), one in
+    six lower case.  annotate=True: (query, kind, distance) instead of the query."""
+    bits = [_bits(s, _SET_BITS) for s in pool]
+    out = []
+
+    def fill(kind, want_kind, d, count):
+        got, turn = 0, rng.randrange(12)
+        for attempt in range(40 * count + 40):
+            if got >= count:
+                break
+            q = crowded_query(rng, pool, kind, d, turn + attempt)
+            if q is None:
+                continue
+            k, dist, _ = crowded_outcome(bits, q, budget)
+            ok = (k == "miss" and dist == budget + 1) if want_kind == "miss" else (k == want_kind and dist == d)
+            if ok:
+                out.append((q, want_kind, d))
+                got += 1
+
+    for d in range(1, budget + 1):
+        fill("tie", "tie", d, (36 * n) // (100 * budget))
+        fill("hit", "hit", d, (36 * n) // (100 * budget))
+    fill("hit", "miss", budget + 1, (16 * n) // 100)
+    exact = [s for s in pool if set(s) <= set(BASES)]
+    while len(out) < n:
+        out.append((rng.choice(exact), "hit", 0))
+    rng.shuffle(out)
+    P = pool.positions
+    for i, (q, kind, d) in enumerate(out):
+        if i % 8 == 3:
+            at = rng.choice(P) if i % 16 == 3 else rng.randrange(len(q))
+            q = q[:at] + rng.choice("NnX.") + q[at + 1:]
+            k, dist, _ = crowded_outcome(bits, q, budget)
+            kind, d = k, dist
+        if i % 6 == 1:
+            q = q.lower() if i % 12 == 1 else "".join(ch.lower() if rng.random() < 0.5 else ch for ch in q)
+        out[i] = (q, kind, d)
+    return out if annotate else [q for q, _, _ in out]
+
+
+def _embed(rng, template: str, inserts: list, c: int, pad: int) -> str:
+    """The construct with c substitutions in its constant bases, random bases around it."""
+    core = list(fill_template(template, inserts))
+    const = [i for i, ch in enumerate(template) if ch != "-"]
+    for p in rng.sample(const, c):
+        core[p] = rng.choice([b for b in BASES if b != core[p]])
+    return rand_seq(rng, rng.randint(0, pad)) + "".join(core) + rand_seq(rng, rng.randint(0, pad))
+
+
+def crowded_match_case(seed: int, length: int, budget: int, reverse: bool, n: int = 200) -> dict:
+    """matchBarcodes over a crowded pool; reverse=True hands the same queries over reverse-complemented."""
+    rng = random.Random(f"match {seed} {length} {budget}")
+    pool = crowded_pool(rng, length, budget)
+    seqs = crowded_queries(rng, pool, budget, n)
+    if reverse:
+        seqs = [rc(s) for s in seqs]
+    return dict(kind="match", sequences=seqs, choices=list(pool), substitutions=budget, reverse=reverse)
+
+
+def crowded_single_case(seed: int, length: int, budget: int, use_first: bool, n_reads: int = 2000) -> dict:
+    """countSingleBarcodes, both strands, flanks of 10 constant bases: a read with c = 0..budget substitutions in the flanks
+    carries a query built for the remaining cap of budget - c (a few carry one substitution too many); where two constructs
+    fit into a read (80 bases, 150 for keys beyond 64), one read in ten holds a second one right behind the first."""
+    rng = random.Random(f"single {seed} {length} {budget}")
+    pool = crowded_pool(rng, length, budget)
+    template = rand_seq(rng, 10) + "-" * length + rand_seq(rng, 10)
+    per_cap = [crowded_queries(rng, pool, cap, 120) for cap in range(budget + 1)]
+    longest = 150 if length > 64 else 80
+    pad = min(10, longest - len(template)) // 2
+
+    def construct():
+        c = rng.choice(list(range(budget + 1)) * 3 + [budget + 1])
+        q = rng.choice(per_cap[max(budget - c, 0)])
+        return _embed(rng, template, [q], c, 0)
+
+    reads = []
+    for _ in range(n_reads):
+        one = construct()
+        if rng.random() < 0.1 and 2 * len(template) <= longest:
+            read = one + construct()
+        else:
+            read = rand_seq(rng, rng.randint(0, pad)) + one + rand_seq(rng, rng.randint(0, pad))
+        reads.append(rc(read) if rng.random() < 0.5 else read)
+    return dict(kind="single", template=template, strand=2, pool=list(pool), mismatches=budget, use_first=use_first, reads=reads)
+
+
+def crowded_combo_case(seed: int, lens: tuple, budget: int, use_first: bool = True, n_reads: int = 2000) -> dict:
+    """countComboBarcodes, both pools crowded, both strands.  The two regions share one budget, spent in order (SURVEY.md
+    A.5): the first region's query lies at a known distance d0 from its entry -- 0, 1, all of the budget, or anything
+    between -- and the second region's query is built for the cap of budget - d0 - c that is left."""
+    rng = random.Random(f"combo {seed} {lens} {budget}")
+    p0, p1 = crowded_pool(rng, lens[0], budget), crowded_pool(rng, lens[1], budget)
+    template = rand_seq(rng, 8) + "-" * lens[0] + rand_seq(rng, 6) + "-" * lens[1] + rand_seq(rng, 8)
+    first = crowded_queries(rng, p0, budget, 240, annotate=True)
+    by_d = {}
+    for q, kind, d in first:
+        by_d.setdefault(d if kind == "hit" else -1, []).append(q)         # -1: ties and misses
+    rest = [crowded_queries(rng, p1, cap, 120) for cap in range(budget + 1)]
+    reads = []
+    for _ in range(n_reads):
+        d0 = rng.choice([0, 1, budget, budget, -1] + list(range(budget + 1)))
+        d0 = d0 if d0 in by_d else 0
+        c = rng.choice([0, 0, 0, 1]) if d0 >= 0 and d0 < budget else 0
+        q0 = rng.choice(by_d[d0])
+        q1 = rng.choice(rest[max(budget - max(d0, 0) - c, 0)])
+        read = _embed(rng, template, [q0, q1], c, 6)
+        if rng.random() < 0.08:
+            read += _embed(rng, template, [rng.choice(by_d[0]), rng.choice(rest[budget])], 0, 0)
+        reads.append(rc(read) if rng.random() < 0.5 else read)
+    return dict(kind="combo", template=template, strand=2, pool0=list(p0), pool1=list(p1), mismatches=budget, use_first=use_first, reads=reads)
+
+
+def crowded_dual_case(seed: int, lens: tuple, budgets: tuple, randomized: bool, use_first: bool, n_reads: int = 1500) -> dict:
+    """countDualBarcodes (and its diagnostics form, and countPairedComboBarcodes over the distinct barcodes).  Mate 1's
+    barcodes form a crowded pool: near a centre, five or more of them lie within the cap, more than pair_match gathers
+    before it falls back to the nested search.  Mate 2's form stars of three entries, centres far apart: never more than
+    four within the cap.  The valid pairs are a strict subset of the cross product in which barcodes recur (several rows
+    per barcode): every mate-1 barcode has one or two partners, and two arms p, r of each mate-1 star share a partner, a
+    third arm of the star has another.  Read pairs: the centre of a mate-1 star, all its arms within the cap; a tie between the two arms over their shared partner (two valid pairs
+    at the same total), the same tie over the other arm's partner (only invalid pairs within the caps) or with one arm
+    nearer (a unique best pair), a valid row with each mate near its barcode, or two unrelated queries.
+    case["probes"] holds the (query 1, query 2) of every pair as built, before flanks, padding and strands."""
+    rng = random.Random(f"dual {seed} {lens} {budgets}")
+    l1, l2 = lens
+    m1, m2 = budgets
+    u1 = crowded_pool(rng, l1, m1, iupac=False)
+    if l2 < CROWDED_SHORT:       # short keys: four centres that differ nearly everywhere, over all four bases
+        u2 = crowded_pool(rng, l2, m2, centres=4, arms=2, doubles=0, iupac=False, alphabet=BASES, min_dist=l2 - 1)
+    else:
+        u2 = crowded_pool(rng, l2, m2, centres=5, arms=2, doubles=0, iupac=False)
+    s1, s2 = set(u1), list(u2)
+    rows, special = [], []
+    for c, alt, _ in u1.stars:
+        arms = [p for p in sorted(alt) if substitute(c, p, alt[p]) in s1]
+        rng.shuffle(arms)
+        if len(arms) >= 3:
+            p, r, t = arms[:3]
+            x, y = rng.sample(s2, 2)
+            rows += [(substitute(c, p, alt[p]), x), (substitute(c, r, alt[r]), x), (substitute(c, t, alt[t]), y)]
+            special.append((len(special), p, r, t, x, y))
+    taken = {a for a, _ in rows}
+    for a in u1:
+        if a not in taken:
+            rows += [(a, b) for b in rng.sample(s2, rng.choice([1, 1, 2]))]
+    rng.shuffle(rows)
+    t1 = rand_seq(rng, 6) + "-" * l1 + rand_seq(rng, 6)
+    t2 = rand_seq(rng, 6) + "-" * l2 + rand_seq(rng, 6)
+    q1s = [crowded_queries(rng, u1, cap, 120) for cap in range(m1 + 1)]
+    q2s = [crowded_queries(rng, u2, cap, 120) for cap in range(m2 + 1)]
+    b1, b2 = [_bits(s, _SET_BITS) for s in u1], [_bits(s, _SET_BITS) for s in u2]
+
+    def near(pool, bits, target, cap, tries=30):
+        """a query whose unique hit within cap is `target` (at any distance), or the target itself"""
+        want = pool.index(target)
+        for _ in range(tries):
+            d = rng.randint(0, cap)
+            q = list(target)
+            for s in _spread(rng, len(target), pool.positions, d, rng.randrange(24)):
+                q[s] = rng.choice([b for b in BASES if b != target[s]])
+            q = "".join(q)
+            if crowded_outcome(bits, q, cap)[::2] == ("hit", want):
+                return q
+        return target
+
+    reads1, reads2, probes = [], [], []
+    for _ in range(n_reads):
+        u = rng.random()
+        c1, c2 = rng.choice([0, 0, 0, 1]) if m1 else 0, rng.choice([0, 0, 0, 1]) if m2 else 0
+        cap1, cap2 = m1 - c1, m2 - c2
+        if u < 0.25 and special and cap1 >= 1:
+            k, p, r, t, x, y = rng.choice(special)
+            c, alt, _ = u1.stars[k]
+            d = rng.randint(1, cap1)
+            q = list(c)
+            q[p], q[r] = alt[p], alt[r]
+            for s in _spread(rng, l1, u1.positions, d - 1, rng.randrange(24), fixed=(p, r, t)):
+                q[s] = _third(rng, u1, k, s)
+            if rng.random() < 0.3 and d < cap1:         # one arm nearer: a unique best pair
+                q[r] = c[r]
+            a = "".join(q)
+            b = near(u2, b2, x if rng.random() < 0.6 else y, cap2)
+        elif u < 0.45 and special and cap1 >= 1:        # at the centre: every arm of the star lies within the cap
+            k, p, r, t, x, y = rng.choice(special)
+            a = crowded_query(rng, u1, "centre", rng.randint(0, cap1 - 1), rng.randrange(24), star=k)
+            b = near(u2, b2, rng.choice([x, y]), cap2)
+        elif u < 0.8:
+            x, y = rng.choice(rows)
+            a, b = near(u1, b1, x, cap1), near(u2, b2, y, cap2)
+        else:
+            a, b = rng.choice(q1s[cap1]), rng.choice(q2s[cap2])
+        probes.append((a, b))
+        a, b = _embed(rng, t1, [a], c1, 8), _embed(rng, t2, [b], c2, 8)
+        if l1 < CROWDED_SHORT and rng.random() < 0.1:       # a second construct on mate 1: first and best differ
+            a += _embed(rng, t1, [near(u1, b1, rng.choice(rows)[0], m1)], 0, 0)
+        if randomized and rng.random() < 0.5:
+            a, b = b, a
+        reads1.append(a)
+        reads2.append(b)
+    return dict(kind="dual", template1=t1, reverse1=False, mismatches1=m1, pool1=[a for a, _ in rows],
+                template2=t2, reverse2=False, mismatches2=m2, pool2=[b for _, b in rows],
+                randomized=randomized, use_first=use_first, reads1=reads1, reads2=reads2, probes=probes)
+
+
+def crowded_dual_single_end_case(seed: int, lens: tuple, budget: int, use_first: bool = True, n_reads: int = 1500) -> dict:
+    """countDualBarcodesSingleEnd (and its diagnostics form): the rows of a crowded pool of the combined length, cut into
+    the regions -- a row that differs from its centre in one region shares the other region's barcode with it, so the
+    barcodes of a region recur over several rows."""
+    rng = random.Random(f"dual_single_end {seed} {lens} {budget}")
+    total = sum(lens)
+    pool = crowded_pool(rng, total, budget, iupac=False)
+    cuts = [sum(lens[:i]) for i in range(len(lens) + 1)]
+
+    def cut(s):
+        return [s[a:b] for a, b in zip(cuts, cuts[1:])]
+    pools = [list(col) for col in zip(*(cut(s) for s in pool))]
+    template = rand_seq(rng, 8) + "".join("-" * n + rand_seq(rng, 5 if i + 1 < len(lens) else 8) for i, n in enumerate(lens))
+    per_cap = [crowded_queries(rng, pool, cap, 120) for cap in range(budget + 1)]
+    reads = []
+    for _ in range(n_reads):
+        c = rng.choice(list(range(budget + 1)) * 3 + [budget + 1])
+        read = _embed(rng, template, cut(rng.choice(per_cap[max(budget - c, 0)])), c, 8)
+        reads.append(rc(read) if rng.random() < 0.5 else read)
+    return dict(kind="dual_single_end", template=template, strand=2, pools=pools, mismatches=budget, use_first=use_first, reads=reads)
+
+
+# The crowded cases with a kaori golden (tests/golden/kaori_crowded.json, by name), one seed each.
+CROWDED_MATCH_LENGTHS = (8, 20, 32, 33, 40, 64, 65, 128, 129, 192, 256)
+CROWDED_MATCH_BUDGETS = (0, 1, 2, 3, 4, 5)
+CROWDED_SINGLE_LENGTHS = (20, 40, 100)
+CROWDED_SINGLE_BUDGETS = (1, 2, 3, 4)
+CROWDED_COMBO_LENGTHS = ((12, 10), (40, 8))
+CROWDED_COMBO_BUDGETS = (2, 4)
+CROWDED_SEED = 20261018
+
+
+def crowded_golden_cases() -> dict:
+    """name -> zero-argument builder of every crowded match, single and combo case"""
+    out = {}
+    for length in CROWDED_MATCH_LENGTHS:
+        for budget in CROWDED_MATCH_BUDGETS:
+            for reverse in (False, True):
+                out[f"match-{length}-{budget}-{'rev' if reverse else 'fwd'}"] = \
+                    lambda a=length, b=budget, r=reverse: crowded_match_case(CROWDED_SEED, a, b, r)
+    for length in CROWDED_SINGLE_LENGTHS:
+        for budget in CROWDED_SINGLE_BUDGETS:
+            for first in (True, False):
+                out[f"single-{length}-{budget}-{'first' if first else 'best'}"] = \
+                    lambda a=length, b=budget, f=first: crowded_single_case(CROWDED_SEED, a, b, f)
+    for lens in CROWDED_COMBO_LENGTHS:
+        for budget in CROWDED_COMBO_BUDGETS:
+            out[f"combo-{lens[0]}x{lens[1]}-{budget}"] = lambda a=lens, b=budget: crowded_combo_case(CROWDED_SEED, a, b)
+    return out
