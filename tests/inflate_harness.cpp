@@ -1,9 +1,13 @@
 // inflate_harness.cpp -- host-side differential test of csrc/scg_inflate.h (the per-lane DEFLATE decoder of the device
 // inflate kernel) against zlib.  Built by tests/test_inflate_cpu.py with g++ -fsanitize=address,undefined.
 //   inflate_harness <seed> <rounds>
+//   inflate_harness --streams FILE
 // Valid streams of many shapes (levels 0-9, Z_FIXED / Z_HUFFMAN_ONLY / Z_RLE / Z_FILTERED, FASTQ-like, random, runs)
 // must decode identically; corrupted streams must be rejected whenever zlib rejects them and, when accepted, give
 // exactly zlib's output; nothing may read or write out of bounds (ASan) or run away.
+// --streams: FILE holds hand-written streams (tests/test_deflate_shapes_cpu.py), entry after entry: u32 stream bytes, u32 text
+// bytes, u8 valid, the stream, the text (little endian).  Each runs through ours(): accept / reject must equal zlib's verdict
+// and the entry's flag, and accepted text must equal the entry's.
 #include "../screencounter_amd/csrc/scg_inflate.h"
 
 #include <zlib.h>
@@ -109,7 +113,41 @@ static int ours(const std::vector<uint8_t>& c, size_t n, std::vector<uint8_t>& o
     return rc;
 }
 
+static int run_streams(const char* path) {
+    FILE* f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "FAIL cannot open %s\n", path); return 1; }
+    long entries = 0, valid = 0;
+    for (;;) {
+        uint8_t head[9];
+        const size_t got_head = fread(head, 1, sizeof(head), f);
+        if (got_head == 0) break;
+        if (got_head != sizeof(head)) { fprintf(stderr, "FAIL truncated container (entry %ld)\n", entries); return 1; }
+        uint32_t clen, tlen;
+        memcpy(&clen, head, 4);
+        memcpy(&tlen, head + 4, 4);
+        const bool want = head[8] != 0;
+        std::vector<uint8_t> c(clen), text(tlen);
+        if ((clen && fread(c.data(), 1, clen, f) != clen) || (tlen && fread(text.data(), 1, tlen, f) != tlen)) {
+            fprintf(stderr, "FAIL truncated container (entry %ld)\n", entries);
+            return 1;
+        }
+        std::vector<uint8_t> zout, mine;
+        const bool zok = zlib_inflate(c, tlen, zout);
+        const int rc = ours(c, tlen, mine);
+        const bool ok = rc == scginf::INFLATE_OK;
+        if (zok != want) { fprintf(stderr, "FAIL entry %ld: zlib %s a stream marked %s\n", entries, zok ? "accepts" : "rejects", want ? "valid" : "invalid"); return 1; }
+        if (ok != zok) { fprintf(stderr, "FAIL entry %ld: rc %d where zlib %s\n", entries, rc, zok ? "accepts" : "rejects"); return 1; }
+        if (ok && (mine != text || zout != text)) { fprintf(stderr, "FAIL entry %ld: the text differs from the intended one\n", entries); return 1; }
+        ++entries;
+        valid += want;
+    }
+    fclose(f);
+    printf("ok: %ld streams (%ld valid, %ld invalid)\n", entries, valid, entries - valid);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc > 2 && strcmp(argv[1], "--streams") == 0) return run_streams(argv[2]);
     const uint64_t seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
     const int rounds = argc > 2 ? atoi(argv[2]) : 200;
     std::mt19937_64 rng(seed);
