@@ -1,10 +1,28 @@
-// scg_api.cpp -- the C ABI (include/scg.h): every entry point, over the plans (scg_plan.cpp) and the file
-// entries (scg_files.cpp, scg_results.cpp).
+// scg_api.cpp -- the C ABI (include/scg.h): every entry point, over the plans (scg_plan.cpp), the file entries
+// (scg_files.cpp) and the read-out of results (scg_results.cpp).  An entry checks its pointers, keeps the reference's
+// order of errors, and calls; no pipeline lives here.
 //
 // Host-side counterpart of the reference's Rcpp glue (src/count_single_barcodes.cpp,
 // src/count_combo_barcodes_single.cpp, src/count_dual_barcodes.cpp, src/match_barcodes.cpp): same argument order,
 // same checks in the same order, status + message instead of exceptions.
 #include "scg_internal.hpp"
+
+namespace {
+
+// What the plan factories share: every argument check (`compile`: host work only) before any device work, then the upload;
+// *plan_out is null whenever the call fails.
+int new_plan(scg_plan** plan_out, int device, char* err, size_t errcap, const Compile& compile, void (*after_upload)(scg_plan*) = nullptr) {
+    return guarded(err, errcap, [&] {
+        if (!plan_out) throw Error(SCG_ERR_INVALID, "null argument");
+        *plan_out = nullptr;
+        std::unique_ptr<scg_plan> P = compile();
+        P->to_device(device);
+        if (after_upload) after_upload(P.get());
+        *plan_out = P.release();
+    });
+}
+
+} // namespace
 
 // -------------------------------------------------------------------------------------------------
 // C ABI
@@ -54,12 +72,8 @@ int scg_parse_fastq(const char* path, char** seqs_out, uint64_t** offsets_out, i
             all.seqs.insert(all.seqs.end(), b.seqs.begin(), b.seqs.end());
             for (int64_t i = 1; i <= b.size(); ++i) all.offsets.push_back(base + b.offsets[i]);
         }
-        char* s = static_cast<char*>(std::malloc(all.seqs.size() + 1));
-        uint64_t* o = static_cast<uint64_t*>(std::malloc(sizeof(uint64_t) * all.offsets.size()));
-        if (!s || !o) { std::free(s); std::free(o); throw std::bad_alloc(); }
-        if (!all.seqs.empty()) std::memcpy(s, all.seqs.data(), all.seqs.size());
-        std::memcpy(o, all.offsets.data(), sizeof(uint64_t) * all.offsets.size());
-        *seqs_out = s; *offsets_out = o; *n_reads_out = all.size();
+        vectors_out(all.seqs, 1, all.offsets, 0, seqs_out, offsets_out);
+        *n_reads_out = all.size();
     });
 }
 
@@ -87,13 +101,9 @@ int scg_fastq_text_windows(const char* path, int64_t window_bytes, int nthreads,
             }
             if (!again) break;
         }
-        char* t = static_cast<char*>(std::malloc(all.size() + 1));
-        int64_t* c = static_cast<int64_t*>(std::malloc(sizeof(int64_t) * cuts.size()));
-        if (!t || !c) { std::free(t); std::free(c); throw std::bad_alloc(); }
-        if (!all.empty()) std::memcpy(t, all.data(), all.size());
-        std::memcpy(c, cuts.data(), sizeof(int64_t) * cuts.size());
-        *text_out = t; *n_bytes_out = static_cast<int64_t>(all.size());
-        *cuts_out = c; *n_windows_out = static_cast<int64_t>(cuts.size()) - 1;
+        vectors_out(all, 1, cuts, 0, text_out, cuts_out);
+        *n_bytes_out = static_cast<int64_t>(all.size());
+        *n_windows_out = static_cast<int64_t>(cuts.size()) - 1;
     });
 }
 
@@ -121,12 +131,7 @@ int scg_fastq_scan_windows(const char* path, int64_t window_bytes, int nthreads,
                 for (uint32_t r = 0; r < g.n_records; ++r) offsets.push_back(base + offs[g.off_at + r + 1]);
             }
         }
-        char* t = static_cast<char*>(std::malloc(all.size() + 1));
-        uint64_t* o = static_cast<uint64_t*>(std::malloc(sizeof(uint64_t) * offsets.size()));
-        if (!t || !o) { std::free(t); std::free(o); throw std::bad_alloc(); }
-        if (!all.empty()) std::memcpy(t, all.data(), all.size());
-        std::memcpy(o, offsets.data(), sizeof(uint64_t) * offsets.size());
-        *seqs_out = t; *offsets_out = o;
+        vectors_out(all, 1, offsets, 0, seqs_out, offsets_out);
         *n_reads_out = static_cast<int64_t>(offsets.size()) - 1;
         *n_windows_out = n_windows;
     });
@@ -159,13 +164,9 @@ int scg_bgzf_member_batches(const char* path, int64_t staging_bytes, int64_t tex
             ++batches;
             if (last) break;
         }
-        uint32_t* t = static_cast<uint32_t*>(std::malloc(sizeof(uint32_t) * (table.size() + 1)));
-        char* p = static_cast<char*>(std::malloc(all.size() + 1));
-        if (!t || !p) { std::free(t); std::free(p); throw std::bad_alloc(); }
-        if (!table.empty()) std::memcpy(t, table.data(), sizeof(uint32_t) * table.size());
-        if (!all.empty()) std::memcpy(p, all.data(), all.size());
-        *table_out = t; *n_members_out = static_cast<int64_t>(table.size() / 6);
-        *payloads_out = p; *n_payload_bytes_out = static_cast<int64_t>(all.size());
+        vectors_out(table, 1, all, 1, table_out, payloads_out);
+        *n_members_out = static_cast<int64_t>(table.size() / 6);
+        *n_payload_bytes_out = static_cast<int64_t>(all.size());
         *n_batches_out = batches;
     });
 }
@@ -190,44 +191,31 @@ int scg_set_devices(const int* devices, int n, char* err, size_t errcap) {
 
 int scg_plan_single(scg_plan** plan_out, const char* constant, int strand, const char* const* pool, int32_t n_pool,
                     int mismatches, int use_first, int device, char* err, size_t errcap) {
-    return guarded(err, errcap, [&] {
-        if (!plan_out) throw Error(SCG_ERR_INVALID, "null argument");
-        auto P = compile_single(constant, strand, pool, n_pool, mismatches, use_first);
-        P->to_device(device);
-        *plan_out = P.release();
+    return new_plan(plan_out, device, err, errcap, [&] {
+        return compile_single(constant, strand, pool, n_pool, mismatches, use_first);
     });
 }
 
 int scg_plan_combo(scg_plan** plan_out, const char* constant, int strand, const char* const* pool0, int32_t n_pool0,
                    const char* const* pool1, int32_t n_pool1, int mismatches, int use_first,
                    int device, char* err, size_t errcap) {
-    return guarded(err, errcap, [&] {
-        if (!plan_out) throw Error(SCG_ERR_INVALID, "null argument");
-        auto P = compile_combo(constant, strand, pool0, n_pool0, pool1, n_pool1, mismatches, use_first);
-        P->to_device(device);
-        *plan_out = P.release();
+    return new_plan(plan_out, device, err, errcap, [&] {
+        return compile_combo(constant, strand, pool0, n_pool0, pool1, n_pool1, mismatches, use_first);
     });
 }
 
 int scg_plan_dual(scg_plan** plan_out, const char* constant1, int reverse1, int mismatches1, const char* const* pool1,
                   const char* constant2, int reverse2, int mismatches2, const char* const* pool2,
                   int32_t n_pool, int randomized, int use_first, int diagnostics, int device, char* err, size_t errcap) {
-    return guarded(err, errcap, [&] {
-        if (!plan_out) throw Error(SCG_ERR_INVALID, "null argument");
-        auto P = compile_dual(constant1, reverse1, mismatches1, pool1, constant2, reverse2, mismatches2, pool2, n_pool, randomized, use_first, diagnostics);
-        P->to_device(device);
-        *plan_out = P.release();
+    return new_plan(plan_out, device, err, errcap, [&] {
+        return compile_dual(constant1, reverse1, mismatches1, pool1, constant2, reverse2, mismatches2, pool2, n_pool, randomized, use_first, diagnostics);
     });
 }
 
 int scg_plan_dual_single_end(scg_plan** plan_out, const char* constant, int strand, const char* const* const* pools, const int32_t* n_pools,
                              int32_t n_regions, int mismatches, int use_first, int device, char* err, size_t errcap) {
-    return guarded(err, errcap, [&] {
-        if (!plan_out) throw Error(SCG_ERR_INVALID, "null argument");
-        *plan_out = nullptr;
-        auto P = compile_dual_single_end(constant, strand, pools, n_pools, n_regions, mismatches, use_first);
-        P->to_device(device);
-        *plan_out = P.release();
+    return new_plan(plan_out, device, err, errcap, [&] {
+        return compile_dual_single_end(constant, strand, pools, n_pools, n_regions, mismatches, use_first);
     });
 }
 
@@ -235,26 +223,17 @@ int scg_plan_paired_combo(scg_plan** plan_out,
                           const char* constant1, int reverse1, int mismatches1, const char* const* pool1, int32_t n_pool1,
                           const char* constant2, int reverse2, int mismatches2, const char* const* pool2, int32_t n_pool2,
                           int randomized, int use_first, int device, char* err, size_t errcap) {
-    return guarded(err, errcap, [&] {
-        if (!plan_out) throw Error(SCG_ERR_INVALID, "null argument");
-        *plan_out = nullptr;
-        auto P = compile_paired_combo(constant1, reverse1, mismatches1, pool1, n_pool1, constant2, reverse2, mismatches2, pool2, n_pool2,
-                                      randomized, use_first);
-        P->to_device(device);
-        *plan_out = P.release();
+    return new_plan(plan_out, device, err, errcap, [&] {
+        return compile_paired_combo(constant1, reverse1, mismatches1, pool1, n_pool1, constant2, reverse2, mismatches2, pool2, n_pool2,
+                                    randomized, use_first);
     });
 }
 
 int scg_plan_random(scg_plan** plan_out, const char* constant, int strand, int mismatches, int use_first,
                     int device, char* err, size_t errcap) {
-    return guarded(err, errcap, [&] {
-        if (!plan_out) throw Error(SCG_ERR_INVALID, "null argument");
-        *plan_out = nullptr;
-        auto P = compile_random(constant, strand, mismatches, use_first);   // every argument check before any device work
-        P->to_device(device);
-        random_to_device(P.get());
-        *plan_out = P.release();
-    });
+    return new_plan(plan_out, device, err, errcap, [&] {
+        return compile_random(constant, strand, mismatches, use_first);
+    }, random_to_device);
 }
 
 int scg_plan_read_random(scg_plan* plan, char** sequences_out, int32_t** freq_out, int64_t* k_out, int32_t* length_out, int64_t* total_out,
@@ -299,9 +278,7 @@ int scg_plan_reset(scg_plan* plan, void* stream, char* err, size_t errcap) {
         }
         HIP_CHECK(hipMemsetAsync(plan->counters, 0, static_cast<size_t>(plan->n_counters) * sizeof(int32_t), static_cast<hipStream_t>(stream)));
         HIP_CHECK(hipMemsetAsync(plan->error_flag.p, 0, sizeof(int32_t), static_cast<hipStream_t>(stream)));
-        for (auto& kv : plan->pair_stream) {
-            if (kv.second.pending) { HIP_CHECK(hipEventSynchronize(kv.second.done)); kv.second.pending = 0; }
-        }
+        drop_pending_pairs(plan);
         plan->sparse_counts.clear();
         plan->total = 0;
     });
@@ -349,10 +326,7 @@ int scg_plan_read_combinations(scg_plan* plan, int32_t** indices_out, int32_t** 
         if (plan->kind != scg_plan::COMBO) throw Error(SCG_ERR_INVALID, "not a combination plan");
         DeviceGuard g(plan->device);
         HIP_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-        std::vector<int32_t> cells(static_cast<size_t>(plan->n_counters) + 1);
-        read_counters(plan, cells.data());
-        if (plan->sparse) { retire_all_pairs(plan); combos_from_sparse(plan->sparse_counts, indices_out, freq_out, k_out); }
-        else combo_compact(cells.data(), plan->n_pool[0], plan->n_pool[1], indices_out, freq_out, k_out);
+        result_combinations(std::vector<scg_plan*>(1, plan), indices_out, freq_out, k_out, nullptr);
         if (total_out) *total_out = plan->total;
     });
 }
@@ -402,8 +376,7 @@ int scg_count_single_barcodes(const char* path, const char* constant, int strand
             return compile_single(constant, strand, pool, n_pool, mismatches, use_first);   // :31-47
         });
         tr.mark("compile + count");
-        set->read(counts_out);
-        *total_out = narrow_total(set->total());
+        result_counts(set->all(), counts_out, total_out);
         tr.mark("read counters");
         set.reset();
         tr.mark("release the plan");
@@ -421,12 +394,7 @@ int scg_count_combo_barcodes_single(const char* path, const char* constant, int 
         auto set = compile_and_count_single_end(path, fq, nthreads, [&] {
             return compile_combo(constant, strand, pool0, n_pool0, pool1, n_pool1, mismatches, use_first);
         });
-        std::vector<int32_t> cells(static_cast<size_t>(set->first()->n_counters) + 1);
-        set->read(cells.data());
-        const int32_t total = narrow_total(set->total());
-        if (set->first()->sparse) combos_from_sparse(set->sparse_merged(), indices_out, freq_out, k_out);
-        else combo_compact(cells.data(), n_pool0, n_pool1, indices_out, freq_out, k_out);
-        *total_out = total;
+        result_combinations(set->all(), indices_out, freq_out, k_out, total_out);
     });
 }
 
@@ -444,8 +412,7 @@ int scg_count_dual_barcodes(const char* path1, const char* constant1, int revers
         auto set = compile_and_count_paired(path1, path2, fq1, fq2, nthreads, [&] {
             return compile_dual(constant1, reverse1, mismatches1, pool1, constant2, reverse2, mismatches2, pool2, n_pool, randomized, use_first);
         });
-        set->read(counts_out);
-        *total_out = narrow_total(set->total());
+        result_counts(set->all(), counts_out, total_out);
     });
 }
 
@@ -486,93 +453,15 @@ int scg_count_dual_barcodes_single_end(const char* path, const char* constant, c
     });
 }
 
-// countRandomBarcodes (src/count_random_barcodes.cpp:41-62, kaori::RandomBarcodeSingleEnd): the device
-// locates the template in every read (same scan kernels, no library), the host cuts the variable region
-// out of its copy of the batch and tallies the strings.  Reproduced quirks of the reference:
-//  * the forward-strand string is the raw read bytes (case preserved);
-//  * on the reverse strand the region is taken at the FORWARD template's offset inside the window
-//    (RandomBarcodeSingleEnd.hpp:103-105 reads variable_regions()[0], not the reverse regions) and then
-//    reverse-complemented with complement_base<true>: ACGTN in either case -> upper case, anything
-//    else is the error "cannot complement unknown base".
-// Output order: byte-wise ascending (the reference iterates an unordered_map; its R caller sorts).
+// countRandomBarcodes: the reader first (src/count_random_barcodes.cpp:42), then the template's checks and the host tally
+// of count_random_file (scg_files.cpp).
 int scg_count_random_barcodes(const char* path, const char* constant, int strand, int mismatches, int use_first, int nthreads,
                               char** sequences_out, int32_t** freq_out, int64_t* k_out, int32_t* length_out, int32_t* total_out,
                               char* err, size_t errcap) {
     return guarded(err, errcap, [&] {
         if (!path || !constant || !sequences_out || !freq_out || !k_out || !length_out || !total_out) throw Error(SCG_ERR_INVALID, "null argument");
-        scg::FastqStream fq(path);                             // reader first (src/count_random_barcodes.cpp:42)
-        std::unique_ptr<scg_plan> P(new scg_plan);
-        P->kind = scg_plan::SINGLE;
-        P->ht1 = scg::parse_template(constant, strand);
-        const ScgTemplate& t = P->ht1.t;
-        if (t.nreg < 1) throw Error(SCG_ERR_INVALID, "expected one variable region in the constant template");
-        if (t.nreg > SCG_MAX_REGIONS) throw Error(SCG_ERR_UNSUPPORTED, "this engine handles templates with at most " + std::to_string(SCG_MAX_REGIONS) + " variable regions");
-        if (mismatches < 0) throw Error(SCG_ERR_INVALID, "negative number of mismatches");
-        P->scan1 = scg::build_scan(t, mismatches);
-        P->max_mm1 = mismatches;
-        P->use_first = use_first != 0;
-        P->n_counters = 0;
-        P->to_device(-1);
-        DeviceGuard g(P->device);
-        const int vstart = t.fstart[0], vlen = t.flen[0];      // forward coordinates on both strands (see above)
-        std::unordered_map<std::string, int32_t> tally;
-        std::string key(static_cast<size_t>(vlen), ' ');
-        ScgSingleParams sp;
-        sp.scan = P->scan1;
-        sp.tmpl = P->d_tmpl1.as<ScgTemplate>();
-        std::memset(&sp.index, 0, sizeof(sp.index));
-        sp.max_mm = mismatches; sp.use_first = P->use_first;
-        sp.fwd = P->ht1.fwd; sp.rev = P->ht1.rev;
-        auto launch = [&](Stager::Slot& s, const ScgReads& R, int64_t n) {
-            s.d_aux.ensure(static_cast<size_t>(n) * sizeof(int32_t));
-            s.h_aux.ensure(static_cast<size_t>(n) * sizeof(int32_t));
-            HIP_CHECK(scg::launch_random(sp, t.len, R, n, s.d_aux.as<int32_t>(), P->error_flag.as<int32_t>(), s.stream));
-            HIP_CHECK(hipMemcpyAsync(s.h_aux.p, s.d_aux.p, static_cast<size_t>(n) * sizeof(int32_t), hipMemcpyDeviceToHost, s.stream));
-            P->total += n;
-        };
-        auto retire = [&](Stager::Slot& s) {
-            const int32_t* hits = s.h_aux.as<int32_t>();
-            const char* seqs = s.h_seqs[0].as<char>();
-            const uint32_t* offs = s.h_offs[0].as<uint32_t>();
-            for (int64_t i = 0; i < s.n_reads; ++i) {
-                const int32_t h = hits[i];
-                if (h < 0) continue;
-                const char* start = seqs + offs[i] + (h >> 1) + vstart;
-                if (!(h & 1)) {
-                    key.assign(start, static_cast<size_t>(vlen));
-                } else {
-                    for (int j = 0; j < vlen; ++j) {
-                        char b = start[vlen - j - 1], o;
-                        switch (b) {                            // kaori/utils.hpp:41-120, complement_base<true>
-                            case 'A': case 'a': o = 'T'; break;
-                            case 'C': case 'c': o = 'G'; break;
-                            case 'G': case 'g': o = 'C'; break;
-                            case 'T': case 't': o = 'A'; break;
-                            case 'N': case 'n': o = 'N'; break;
-                            default: throw Error(SCG_ERR_INVALID, std::string("cannot complement unknown base '") + b + "'");
-                        }
-                        key[static_cast<size_t>(j)] = o;
-                    }
-                }
-                ++tally[key];
-            }
-        };
-        auto restart = [&] { tally.clear(); };
-        count_single_end_file(P.get(), path, fq, nthreads, launch, retire, restart);
-        read_counters(P.get(), nullptr);                       // surfaces the oversize-read flag
-        std::vector<std::pair<std::string, int32_t> > rows(tally.begin(), tally.end());
-        std::sort(rows.begin(), rows.end());
-        const size_t stride = static_cast<size_t>(vlen) + 1;
-        char* so = static_cast<char*>(std::malloc(rows.size() * stride + 1));
-        int32_t* fo = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * (rows.size() + 1)));
-        if (!so || !fo) { std::free(so); std::free(fo); throw std::bad_alloc(); }
-        for (size_t i = 0; i < rows.size(); ++i) {
-            std::memcpy(so + i * stride, rows[i].first.data(), static_cast<size_t>(vlen));
-            so[i * stride + vlen] = 0;
-            fo[i] = rows[i].second;
-        }
-        *sequences_out = so; *freq_out = fo; *k_out = static_cast<int64_t>(rows.size()); *length_out = vlen;
-        *total_out = narrow_total(P->total);
+        scg::FastqStream fq(path);
+        count_random_file(path, fq, constant, strand, mismatches, use_first, nthreads, sequences_out, freq_out, k_out, length_out, total_out);
     });
 }
 
@@ -632,8 +521,7 @@ int scg_count_single_barcodes_files(const char* const* paths, int32_t n_files, c
         PlanSet set(compile_single(constant, strand, pool, n_pool, mismatches, use_first), devices);
         const size_t stride = static_cast<size_t>(n_pool);
         schedule_single_end(n_files, set, paths, nthreads, [&](scg_plan* P, int32_t f) {
-            read_counters(P, counts_out + stride * static_cast<size_t>(f));
-            totals_out[f] = narrow_total(P->total);
+            result_counts(std::vector<scg_plan*>(1, P), counts_out + stride * static_cast<size_t>(f), &totals_out[f]);
         });
     });
 }
@@ -651,13 +539,8 @@ int scg_count_combo_barcodes_single_files(const char* const* paths, int32_t n_fi
             scg::FastqStream probe(paths[0]);
             const std::vector<int> devices = devices_for_files(n_files);
             PlanSet set(compile_combo(constant, strand, pool0, n_pool0, pool1, n_pool1, mismatches, use_first), devices);
-            const size_t cells = static_cast<size_t>(set.first()->n_counters);
             schedule_single_end(n_files, set, paths, nthreads, [&](scg_plan* P, int32_t f) {
-                std::vector<int32_t> dense(cells + 1);
-                read_counters(P, dense.data());
-                totals_out[f] = narrow_total(P->total);
-                if (P->sparse) { retire_all_pairs(P); combos_from_sparse(P->sparse_counts, &indices_out[f], &freq_out[f], &k_out[f]); }
-                else combo_compact(dense.data(), n_pool0, n_pool1, &indices_out[f], &freq_out[f], &k_out[f]);
+                result_combinations(std::vector<scg_plan*>(1, P), &indices_out[f], &freq_out[f], &k_out[f], &totals_out[f]);
             });
         });
     });
@@ -676,16 +559,16 @@ int scg_count_dual_barcodes_files(const char* const* paths1, const char* constan
         PlanSet set(compile_dual(constant1, reverse1, mismatches1, pool1, constant2, reverse2, mismatches2, pool2, n_pool, randomized, use_first), devices);
         const size_t stride = static_cast<size_t>(n_pool);
         schedule_paired(n_files, set, paths1, paths2, nthreads, [&](scg_plan* P, int32_t f) {
-            read_counters(P, counts_out + stride * static_cast<size_t>(f));
-            totals_out[f] = narrow_total(P->total);
+            result_counts(std::vector<scg_plan*>(1, P), counts_out + stride * static_cast<size_t>(f), &totals_out[f]);
         });
     });
 }
 
 // The four entries below check their arguments -- the template and the pools are compiled, host work only -- before any
-// file is opened and any device is touched; then every device gets its plan and takes the files one at a time.  A plan
-// starts every file from reset_plan (counters, sparse combinations, runs in flight, the oversize-read flag), and a file's
-// outputs are read by the function its one-file entry reads them with (result_counts, result_diagnostics).
+// file is opened and any device is touched; then every device gets its plan and takes the files one at a time.  In all
+// seven many-files entries a plan starts every file from reset_plan (counters, sparse combinations, runs in flight, the
+// oversize-read flag), and a file's outputs are read by the function its one-file entry reads them with (result_counts,
+// result_combinations, result_diagnostics).
 
 int scg_count_dual_barcodes_diagnostics_files(const char* const* paths1, const char* constant1, int reverse1, int mismatches1, const char* const* pool1,
                                               const char* const* paths2, const char* constant2, int reverse2, int mismatches2, const char* const* pool2,

@@ -1,5 +1,6 @@
-// scg_files.cpp -- FASTQ files to counts: the host readers (staging of parsed batches), the fall-back ladders that decide
-// which reader takes a file, and the file entries scg_api.cpp calls.  The windowed pipelines are in scg_windows.hpp.
+// scg_files.cpp -- FASTQ files to counts: the host readers (staging of parsed batches) and the host tally of
+// countRandomBarcodes over them, the fall-back ladders that decide which reader takes a file, and the file entries
+// scg_api.cpp calls.  The windowed pipelines are in scg_windows.hpp.
 #include "scg_windows.hpp"
 
 namespace scgapi {
@@ -56,6 +57,76 @@ void count_single_end_file(scg_plan* P, const char* path, scg::FastqStream& fq, 
         s.busy = true;
     }
     st.drain();
+}
+
+// countRandomBarcodes on one file (src/count_random_barcodes.cpp:41-62, kaori::RandomBarcodeSingleEnd): the device
+// locates the template in every read (same scan kernels, no library), the host cuts the variable region
+// out of its copy of the batch and tallies the strings.  Reproduced quirks of the reference:
+//  * the forward-strand string is the raw read bytes (case preserved);
+//  * on the reverse strand the region is taken at the FORWARD template's offset inside the window
+//    (RandomBarcodeSingleEnd.hpp:103-105 reads variable_regions()[0], not the reverse regions) and then
+//    reverse-complemented with complement_base<true>: ACGTN in either case -> upper case, anything
+//    else is the error "cannot complement unknown base".
+// Output order: byte-wise ascending (the reference iterates an unordered_map; its R caller sorts).
+void count_random_file(const char* path, scg::FastqStream& fq, const char* constant, int strand, int mismatches, int use_first, int nthreads,
+                       char** sequences_out, int32_t** freq_out, int64_t* k_out, int32_t* length_out, int32_t* total_out) {
+    std::unique_ptr<scg_plan> P = compile_random_template(constant, strand, mismatches, use_first);
+    const ScgTemplate& t = P->ht1.t;
+    P->to_device(-1);
+    DeviceGuard g(P->device);
+    const int vstart = t.fstart[0], vlen = t.flen[0];      // forward coordinates on both strands (see above)
+    std::unordered_map<std::string, int32_t> tally;
+    std::string key(static_cast<size_t>(vlen), ' ');
+    const ScgSingleParams sp = single_params(P.get(), ScgIndex());
+    auto launch = [&](Stager::Slot& s, const ScgReads& R, int64_t n) {
+        s.d_aux.ensure(static_cast<size_t>(n) * sizeof(int32_t));
+        s.h_aux.ensure(static_cast<size_t>(n) * sizeof(int32_t));
+        HIP_CHECK(scg::launch_random(sp, t.len, R, n, s.d_aux.as<int32_t>(), P->error_flag.as<int32_t>(), s.stream));
+        HIP_CHECK(hipMemcpyAsync(s.h_aux.p, s.d_aux.p, static_cast<size_t>(n) * sizeof(int32_t), hipMemcpyDeviceToHost, s.stream));
+        P->total += n;
+    };
+    auto retire = [&](Stager::Slot& s) {
+        const int32_t* hits = s.h_aux.as<int32_t>();
+        const char* seqs = s.h_seqs[0].as<char>();
+        const uint32_t* offs = s.h_offs[0].as<uint32_t>();
+        for (int64_t i = 0; i < s.n_reads; ++i) {
+            const int32_t h = hits[i];
+            if (h < 0) continue;
+            const char* start = seqs + offs[i] + (h >> 1) + vstart;
+            if (!(h & 1)) {
+                key.assign(start, static_cast<size_t>(vlen));
+            } else {
+                for (int j = 0; j < vlen; ++j) {
+                    char b = start[vlen - j - 1], o;
+                    switch (b) {                            // kaori/utils.hpp:41-120, complement_base<true>
+                        case 'A': case 'a': o = 'T'; break;
+                        case 'C': case 'c': o = 'G'; break;
+                        case 'G': case 'g': o = 'C'; break;
+                        case 'T': case 't': o = 'A'; break;
+                        case 'N': case 'n': o = 'N'; break;
+                        default: throw Error(SCG_ERR_INVALID, std::string("cannot complement unknown base '") + b + "'");
+                    }
+                    key[static_cast<size_t>(j)] = o;
+                }
+            }
+            ++tally[key];
+        }
+    };
+    auto restart = [&] { tally.clear(); };
+    count_single_end_file(P.get(), path, fq, nthreads, launch, retire, restart);
+    read_counters(P.get(), nullptr);                       // surfaces the oversize-read flag
+    std::vector<std::pair<std::string, int32_t> > rows(tally.begin(), tally.end());
+    std::sort(rows.begin(), rows.end());
+    const size_t stride = static_cast<size_t>(vlen) + 1;
+    OutPair<char, int32_t> out(rows.size() * stride + 1, rows.size() + 1);
+    for (size_t i = 0; i < rows.size(); ++i) {
+        std::memcpy(out.a + i * stride, rows[i].first.data(), static_cast<size_t>(vlen));
+        out.a[i * stride + vlen] = 0;
+        out.b[i] = rows[i].second;
+    }
+    const int32_t total = narrow_total(P->total);
+    out.release(sequences_out, freq_out);
+    *k_out = static_cast<int64_t>(rows.size()); *length_out = vlen; *total_out = total;
 }
 
 // -------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // scg_internal.hpp -- what the parts of the host side share: error plumbing, device buffers, the plan object, and the
-// functions one part calls in another.  scg_plan.cpp: plan compilation and batch launches; scg_files.cpp: FASTQ files to
-// counts (the fall-back ladders and file entries, over the windows of scg_windows.hpp); scg_results.cpp: devices, plan
-// sets and result shaping; scg_api.cpp: the C entry points of include/scg.h.
+// functions one part calls in another.  scg_plan.cpp: plan compilation, kernel arguments and batch launches; scg_files.cpp:
+// FASTQ files to counts (the host readers, the fall-back ladders and file entries, over the windows of scg_windows.hpp);
+// scg_results.cpp: devices, plan sets and result shaping; scg_api.cpp: the C entry points of include/scg.h.
 #ifndef SCG_INTERNAL_HPP
 #define SCG_INTERNAL_HPP
 #include <hip/hip_runtime_api.h>
@@ -186,6 +186,30 @@ struct DevPairTable {
     }
 };
 
+// Two malloc'd arrays on their way to a caller of the C ABI, who frees them with scg_free: both or std::bad_alloc, and both
+// freed again unless release() hands them over.
+template<class A, class B>
+struct OutPair {
+    A* a;
+    B* b;
+    OutPair(size_t na, size_t nb) : a(static_cast<A*>(std::malloc(sizeof(A) * na))), b(static_cast<B*>(std::malloc(sizeof(B) * nb))) {
+        if (!a || !b) { std::free(a); std::free(b); throw std::bad_alloc(); }
+    }
+    OutPair(const OutPair&) = delete;
+    OutPair& operator=(const OutPair&) = delete;
+    ~OutPair() { std::free(a); std::free(b); }
+    void release(A** a_out, B** b_out) { *a_out = a; *b_out = b; a = nullptr; b = nullptr; }
+};
+// Copies of two vectors as such a pair, with room for slack_a / slack_b more elements behind them (a NUL, or so that no
+// array is empty).
+template<class A, class B>
+void vectors_out(const std::vector<A>& a, size_t slack_a, const std::vector<B>& b, size_t slack_b, A** a_out, B** b_out) {
+    OutPair<A, B> out(a.size() + slack_a, b.size() + slack_b);
+    if (!a.empty()) std::memcpy(out.a, a.data(), sizeof(A) * a.size());
+    if (!b.empty()) std::memcpy(out.b, b.data(), sizeof(B) * b.size());
+    out.release(a_out, b_out);
+}
+
 } // namespace scgapi
 
 using namespace scgapi;
@@ -349,7 +373,6 @@ namespace scgapi {
 typedef std::function<std::unique_ptr<scg_plan>()> Compile;
 
 // ---- scg_plan.cpp ----
-bool general_only(const scg_plan* P);
 int64_t dense_cells();
 ScgReads make_reads(const char* d_seqs, const uint32_t* d_offsets, int32_t fixed_len, int32_t max_len);
 void check_reads_args(const char* d_seqs, const uint32_t* d_offsets, int32_t fixed_len, int64_t n);
@@ -365,6 +388,9 @@ std::unique_ptr<scg_plan> compile_dual_single_end_diag(const char* constant, int
 std::unique_ptr<scg_plan> compile_paired_combo(const char* constant1, int reverse1, int mismatches1, const char* const* pool1, int32_t n1, const char* constant2,
                                                int reverse2, int mismatches2, const char* const* pool2, int32_t n2, int randomized, int use_first);
 void retire_all_pairs(scg_plan* P);
+void drop_pending_pairs(scg_plan* P);
+ScgSingleParams single_params(const scg_plan* P, const ScgIndex& index);
+std::unique_ptr<scg_plan> compile_random_template(const char* constant, int strand, int mismatches, int use_first);
 std::unique_ptr<scg_plan> compile_random(const char* constant, int strand, int mismatches, int use_first);
 void random_to_device(scg_plan* P);
 void random_reset(scg_plan* P, hipStream_t stream);
@@ -447,12 +473,6 @@ struct PlanSet {
     PlanSet(std::unique_ptr<scg_plan> compiled, const std::vector<int>& devices);
     std::vector<scg_plan*> all() const;
     scg_plan* first() const { return plans[0].get(); }
-    int64_t total() const;
-    // Sum of the devices' counters (every count is bounded by the total, which the callers check against int32).
-    void read(int32_t* counts_out) const;
-    void reset() const;
-    // Sparse mode: the combinations of all devices (every batch's runs merged).
-    std::unordered_map<uint64_t, int64_t> sparse_merged() const;
 };
 
 // The switches that steer the file paths (test hooks and tuning aids), read once per file-level call.
@@ -481,6 +501,8 @@ void count_single_end_file(scg_plan* P, const char* path, scg::FastqStream& fq, 
                            const std::function<void(Stager::Slot&, const ScgReads&, int64_t)>& launch = nullptr,
                            const std::function<void(Stager::Slot&)>& retire = nullptr,
                            const std::function<void()>& restart = nullptr);
+void count_random_file(const char* path, scg::FastqStream& fq, const char* constant, int strand, int mismatches, int use_first, int nthreads,
+                       char** sequences_out, int32_t** freq_out, int64_t* k_out, int32_t* length_out, int32_t* total_out);
 void release_cached_slots();
 bool is_parallel_gzip(const scg::TextSource* s);
 void count_single_end(const std::vector<scg_plan*>& plans, const char* path, scg::FastqStream& fq, int nthreads);
@@ -508,10 +530,15 @@ void diagnostics_from_counters(const scg_plan* P, const std::vector<int32_t>& al
                                int32_t* b1, int32_t* b2, const std::unordered_map<uint64_t, int64_t>* sparse = nullptr);
 // One counted input -> the outputs of its entry point.  `plans`: the plans that counted it -- one per device of a one-file
 // entry (their counters are summed, their combinations merged), the worker's own plan in a many-files entry.
+// (the sum of the plans' counters: every count is bounded by the total, which the callers check against int32)
 void read_plans(const std::vector<scg_plan*>& plans, int32_t* counts_out);
 int64_t total_of(const std::vector<scg_plan*>& plans);
+// (sparse mode: the combinations of all plans, every batch's runs merged)
 std::unordered_map<uint64_t, int64_t> sparse_merged(const std::vector<scg_plan*>& plans);
 void result_counts(const std::vector<scg_plan*>& plans, int32_t* counts_out, int32_t* total_out);
+// (combination plans: dense cells compacted, or the merged runs of sparse mode; total_out is null for the plan's own
+// read-out, which reports its 64-bit total)
+void result_combinations(const std::vector<scg_plan*>& plans, int32_t** idx_out, int32_t** freq_out, int64_t* k_out, int32_t* total_out);
 // (diagnostics plans of every kind: include.invalid=TRUE, paired and single-end, and the paired combinations, which have
 // no counts_out; b1_out / b2_out may be null)
 void result_diagnostics(const std::vector<scg_plan*>& plans, int32_t* counts_out, int32_t** idx_out, int32_t** freq_out, int64_t* k_out,

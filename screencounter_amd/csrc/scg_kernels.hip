@@ -1030,11 +1030,16 @@ inline unsigned staged_grid(int64_t n) { return (unsigned)((n + STAGE_BLOCK - 1)
 namespace scg {
 
 // Test hook: SCG_FORCE_GENERAL=1 runs the byte-wise engine alone (read at every launch so that a
-// test process can flip it).  One definition for kernels and host pipelines alike (scg_launch.h).
-bool force_general() {
+// test process can flip it).
+static bool force_general() {
     const char* e = std::getenv("SCG_FORCE_GENERAL");
     return e && *e && *e != '0';
 }
+
+// The staged kernels need every read to fit a tile row (<= 320 bases); batches with longer reads
+// or an unknown maximum length take the byte-wise general kernels.  One answer for the launchers
+// below and for the host, which picks tally mode and the pair search's passes by it (scg_launch.h).
+bool staged_takes(int max_len) { return !force_general() && max_len > 0 && max_len <= 320; }
 
 namespace {
 
@@ -1129,9 +1134,7 @@ template<int NW, int NT> struct LaunchDual {
 
 } // namespace
 
-// The staged kernels need every read to fit a tile row (<= 320 bases); batches with longer reads
-// or an unknown maximum length take the byte-wise general kernels.
-static bool use_general(int max_len) { return force_general() || max_len <= 0 || max_len > 320; }
+static bool use_general(int max_len) { return !staged_takes(max_len); }
 
 hipError_t launch_single(const ScgSingleParams& P, int tmpl_len, const ScgReads& R, int64_t n, const ScgCounters& counts, int32_t* flag, hipStream_t stream) {
     if (n <= 0) return hipSuccess;

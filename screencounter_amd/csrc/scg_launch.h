@@ -9,8 +9,10 @@
 
 namespace scg {
 
-// Test hook: SCG_FORCE_GENERAL=1 (any value but empty / 0) runs the byte-wise engine alone; read at every launch.
-bool force_general();
+// Whether the staged kernels take a batch whose longest read has max_len bases (0: unknown); the byte-wise general
+// kernels take the rest.  Test hook: SCG_FORCE_GENERAL=1 (any value but empty / 0) gives them every batch; read at
+// every launch.
+bool staged_takes(int max_len);
 
 hipError_t launch_single(const ScgSingleParams& P, int tmpl_len, const ScgReads& R, int64_t n, const ScgCounters& counts, int32_t* flag, hipStream_t stream);
 // countRandomBarcodes: d_hits[i] = (position << 1) | reverse of read i's template hit, or -1

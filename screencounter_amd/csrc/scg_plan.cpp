@@ -1,5 +1,6 @@
 // scg_plan.cpp -- plans: host compilation of the templates and libraries (every argument check of the reference's
-// constructors lives here), the combination streams of the sparse mode, and the launch of one batch.
+// constructors lives here, each once), the kernel arguments built from a plan (one builder per struct), the combination
+// streams of the sparse mode, and the launch of one batch.
 //
 // Host-side counterpart of the handler construction in the reference's Rcpp glue (src/count_single_barcodes.cpp,
 // src/count_combo_barcodes_single.cpp, src/count_dual_barcodes.cpp, src/count_dual_barcodes_single_end.cpp).
@@ -20,9 +21,9 @@ scg::HostIndex build_uid_index_class(int cls, const char* const* pool, int32_t n
     return scg::build_uid_index_wide(pool, n, len, max_mm, expansions, n_uid);
 }
 
-// Big keys have the byte-wise general kernels only.
+// Big keys have the byte-wise general kernels only, whatever scg::staged_takes says of the batch.
 bool general_only(const scg_plan* P) {
-    return scg::force_general() || P->tab[0].view.wide == 2 || (P->kind == scg_plan::DUAL_SE_DIAG && P->tab_combined.view.wide == 2);
+    return P->tab[0].view.wide == 2 || (P->kind == scg_plan::DUAL_SE_DIAG && P->tab_combined.view.wide == 2);
 }
 
 // 256 MB of int32 cells: beyond that, combinations are sorted and run-length encoded.  $SCG_DENSE_CELLS moves the limit (the
@@ -55,7 +56,59 @@ void check_reads_args(const char* d_seqs, const uint32_t* d_offsets, int32_t fix
     if (!d_offsets && fixed_len < 0) throw Error(SCG_ERR_INVALID, "negative fixed read length");
 }
 
-// ---- host compilation of the three plan kinds (all reference argument checks live here) ----
+// ---- host compilation of the plan kinds (all reference argument checks live here) ----
+
+// SimpleSingleMatch.hpp:75-83: one variable region, as long as the pool's sequences.
+void check_single_match(const scg::HostTemplate& ht, int plen) {
+    if (ht.t.nreg != 1) throw Error(SCG_ERR_INVALID, "expected one variable region in the constant template");
+    if (ht.t.flen[0] != plen) {
+        throw Error(SCG_ERR_INVALID, "length of barcode_pool sequences (" + std::to_string(plen) +
+                    ") should be the same as the barcode_pool region (" + std::to_string(ht.t.flen[0]) + ")");
+    }
+}
+
+// CombinatorialBarcodesSingleEnd.hpp:86-93, DualBarcodesSingleEnd.hpp:80-87: variable region r against its pool's sequences.
+void check_region_length(const ScgTemplate& t, int r, int plen) {
+    if (t.flen[r] != plen) {
+        throw Error(SCG_ERR_INVALID, "length of variable region " + std::to_string(r + 1) + " (" + std::to_string(t.flen[r]) +
+                    ") should be the same as its sequences (" + std::to_string(plen) + ")");
+    }
+}
+
+// The uid indexes of two pools whose sequences meet as pairs (both mates, or both regions of include.invalid=TRUE), into
+// P->htab[0..1]: class 0, or wide / big for both when either pool has more than 32 bases.
+struct UidIndexes {
+    std::vector<std::vector<int32_t> > exp[2];   // barcode -> the uids of its sequences
+    std::vector<uint64_t> keys[2];               // class 0: uid -> key, for the pair table
+    size_t n_uid[2] = {0, 0};
+
+    UidIndexes(scg_plan* P, const char* const* pool0, int32_t n0, int len0, int mm0, const char* const* pool1, int32_t n1, int len1, int mm1) {
+        if (const int cls = std::max(key_class(len0), key_class(len1))) {
+            P->htab[0] = build_uid_index_class(cls, pool0, n0, len0, mm0, exp[0], n_uid[0]);
+            P->htab[1] = build_uid_index_class(cls, pool1, n1, len1, mm1, exp[1], n_uid[1]);
+        } else {
+            P->htab[0] = scg::build_uid_index(pool0, n0, len0, mm0, exp[0], keys[0]);
+            P->htab[1] = scg::build_uid_index(pool1, n1, len1, mm1, exp[1], keys[1]);
+            n_uid[0] = keys[0].size(); n_uid[1] = keys[1].size();
+        }
+    }
+    // uid -> index of the first barcode that contains the sequence
+    std::vector<int32_t> first(int side) const {
+        std::vector<int32_t> f(n_uid[side], -1);
+        for (size_t i = 0; i < exp[side].size(); ++i) {
+            for (int32_t u : exp[side][i]) if (f[u] < 0) f[u] = static_cast<int32_t>(i);
+        }
+        return f;
+    }
+    // The counters of a diagnostics plan: [n_pool valid][2][n_uid0 x n_uid1], the grid only below the dense limit.
+    void diagnostics_grid(scg_plan* P, int32_t n_pool) const {
+        P->first1 = first(0);
+        P->first2 = first(1);
+        const int64_t cells = static_cast<int64_t>(n_uid[0]) * static_cast<int64_t>(n_uid[1]);
+        P->sparse = cells > dense_cells();
+        P->n_counters = static_cast<int64_t>(n_pool) + 2 + (P->sparse ? 0 : cells);
+    }
+};
 
 std::unique_ptr<scg_plan> compile_single(const char* constant, int strand, const char* const* pool, int32_t n_pool,
                                          int mismatches, int use_first) {
@@ -64,14 +117,7 @@ std::unique_ptr<scg_plan> compile_single(const char* constant, int strand, const
     P->kind = scg_plan::SINGLE;
     int plen = scg::pool_length(pool, n_pool);                 // src/utils.cpp:15-17
     P->ht1 = scg::parse_template(constant, strand);            // src/count_single_barcodes.cpp:37-47, ScanTemplate.hpp:53-95
-    if (P->ht1.t.nreg != 1) {
-        throw Error(SCG_ERR_INVALID, "expected one variable region in the constant template");   // SimpleSingleMatch.hpp:75-77
-    }
-    int vlen = P->ht1.t.flen[0];
-    if (vlen != plen) {                                        // SimpleSingleMatch.hpp:79-83
-        throw Error(SCG_ERR_INVALID, "length of barcode_pool sequences (" + std::to_string(plen) +
-                    ") should be the same as the barcode_pool region (" + std::to_string(vlen) + ")");
-    }
+    check_single_match(P->ht1, plen);
     if (mismatches < 0) throw Error(SCG_ERR_INVALID, "negative number of mismatches");
     // BarcodeSearch.hpp:23-60; barcodes of 33..64 bases take the wide (2 x 64-bit plane) index and kernels
     P->htab[0] = plen > SCG_MAX_BARCODE ? scg::build_index_wide(pool, n_pool, plen, mismatches) : scg::build_index(pool, n_pool, plen, mismatches);
@@ -106,10 +152,7 @@ std::unique_ptr<scg_plan> compile_dual_single_end(const char* constant, int stra
     }
     int total = 0;
     for (int r = 0; r < n_regions; ++r) {                         // :80-87
-        if (plen[r] != t.flen[r]) {
-            throw Error(SCG_ERR_INVALID, "length of variable region " + std::to_string(r + 1) + " (" + std::to_string(t.flen[r]) +
-                        ") should be the same as its sequences (" + std::to_string(plen[r]) + ")");
-        }
+        check_region_length(t, r, plen[r]);
         total += plen[r];
     }
     const int32_t n_choices = n_pools[0];
@@ -144,13 +187,8 @@ std::unique_ptr<scg_plan> compile_combo(const char* constant, int strand,
     if (P->ht1.t.nreg != 2) {                                  // CombinatorialBarcodesSingleEnd.hpp:79-81
         throw Error(SCG_ERR_INVALID, "expected 2 variable regions in the constant template");
     }
-    int lens[2] = {len0, len1};
-    for (int r = 0; r < 2; ++r) {                              // :86-93
-        if (P->ht1.t.flen[r] != lens[r]) {
-            throw Error(SCG_ERR_INVALID, "length of variable region " + std::to_string(r + 1) + " (" + std::to_string(P->ht1.t.flen[r]) +
-                        ") should be the same as its sequences (" + std::to_string(lens[r]) + ")");
-        }
-    }
+    check_region_length(P->ht1.t, 0, len0);                    // :86-93
+    check_region_length(P->ht1.t, 1, len1);
     if (mismatches < 0) throw Error(SCG_ERR_INVALID, "negative number of mismatches");
     // pools of 33..64 bases take the wide (2 x 64-bit plane) index and kernels, longer ones the big one; both pools then, one
     // key width per kernel
@@ -188,37 +226,15 @@ std::unique_ptr<scg_plan> compile_dual(const char* constant1, int reverse1, int 
                     std::to_string(P->ht2.t.flen[0]) + ")");
     }
     if (mismatches1 < 0 || mismatches2 < 0) throw Error(SCG_ERR_INVALID, "negative number of mismatches");
-    std::vector<std::vector<int32_t> > exp1, exp2;
-    std::vector<uint64_t> uk1, uk2;
-    size_t n_uid1 = 0, n_uid2 = 0;
-    if (const int cls = std::max(key_class(len1), key_class(len2))) {     // barcodes of more than 32 bases on either mate: wide / big indexes and kernels for both
-        P->htab[0] = build_uid_index_class(cls, pool1, n_pool, len1, mismatches1, exp1, n_uid1);
-        P->htab[1] = build_uid_index_class(cls, pool2, n_pool, len2, mismatches2, exp2, n_uid2);
-    } else {
-        P->htab[0] = scg::build_uid_index(pool1, n_pool, len1, mismatches1, exp1, uk1);
-        P->htab[1] = scg::build_uid_index(pool2, n_pool, len2, mismatches2, exp2, uk2);
-        n_uid1 = uk1.size(); n_uid2 = uk2.size();
-    }
+    const UidIndexes uid(P.get(), pool1, n_pool, len1, mismatches1, pool2, n_pool, len2, mismatches2);
     P->scan1 = scg::build_scan(P->ht1.t, mismatches1);
     P->scan2 = scg::build_scan(P->ht2.t, mismatches2);
-    P->hpairs = scg::build_pair_table(exp1, uk1, exp2, uk2);   // :138-178 (duplicate pairs => error)
+    P->hpairs = scg::build_pair_table(uid.exp[0], uid.keys[0], uid.exp[1], uid.keys[1]);   // :138-178 (duplicate pairs => error)
     P->n_pool[0] = P->n_pool[1] = n_pool;
     P->n_counters = n_pool;
     if (diagnostics) {
-        // uid -> index of the first barcode that contains the sequence
-        auto firsts = [&](const std::vector<std::vector<int32_t> >& exp, size_t n_uid) {
-            std::vector<int32_t> f(n_uid, -1);
-            for (size_t i = 0; i < exp.size(); ++i) {
-                for (int32_t u : exp[i]) if (f[u] < 0) f[u] = static_cast<int32_t>(i);
-            }
-            return f;
-        };
-        P->first1 = firsts(exp1, n_uid1);
-        P->first2 = firsts(exp2, n_uid2);
-        int64_t cells = static_cast<int64_t>(n_uid1) * static_cast<int64_t>(n_uid2);
-        P->sparse = cells > dense_cells();
+        uid.diagnostics_grid(P.get(), n_pool);
         P->diagnostics = 1;
-        P->n_counters = static_cast<int64_t>(n_pool) + 2 + (P->sparse ? 0 : cells);
     }
     P->max_mm1 = mismatches1; P->max_mm2 = mismatches2;
     P->rev1 = reverse1 != 0; P->rev2 = reverse2 != 0;
@@ -237,30 +253,9 @@ std::unique_ptr<scg_plan> compile_dual_single_end_diag(const char* constant, int
     if (t.nreg != 2) throw Error(SCG_ERR_INVALID, "expected 2 variable regions in the constant template");   // CombinatorialBarcodesSingleEnd.hpp:84-86
     P->kind = scg_plan::DUAL_SE_DIAG;
     P->htab_combined = std::move(P->htab[0]);
-    std::vector<std::vector<int32_t> > exp0, exp1;
-    std::vector<uint64_t> uk0, uk1;
-    size_t n_uid0 = 0, n_uid1 = 0;
-    if (const int cls = std::max(key_class(t.flen[0]), key_class(t.flen[1]))) {
-        P->htab[0] = build_uid_index_class(cls, pools[0], n_pools[0], t.flen[0], mismatches, exp0, n_uid0);
-        P->htab[1] = build_uid_index_class(cls, pools[1], n_pools[1], t.flen[1], mismatches, exp1, n_uid1);
-    } else {
-        P->htab[0] = scg::build_uid_index(pools[0], n_pools[0], t.flen[0], mismatches, exp0, uk0);
-        P->htab[1] = scg::build_uid_index(pools[1], n_pools[1], t.flen[1], mismatches, exp1, uk1);
-        n_uid0 = uk0.size(); n_uid1 = uk1.size();
-    }
-    auto firsts = [&](const std::vector<std::vector<int32_t> >& exp, size_t n_uid) {
-        std::vector<int32_t> f(n_uid, -1);
-        for (size_t i = 0; i < exp.size(); ++i) {
-            for (int32_t u : exp[i]) if (f[u] < 0) f[u] = static_cast<int32_t>(i);
-        }
-        return f;
-    };
-    P->first1 = firsts(exp0, n_uid0);
-    P->first2 = firsts(exp1, n_uid1);
-    int64_t cells = static_cast<int64_t>(n_uid0) * static_cast<int64_t>(n_uid1);
-    P->sparse = cells > dense_cells();
+    const UidIndexes uid(P.get(), pools[0], n_pools[0], t.flen[0], mismatches, pools[1], n_pools[1], t.flen[1], mismatches);
+    uid.diagnostics_grid(P.get(), P->n_pool[0]);
     P->n_pool[1] = P->n_pool[0];
-    P->n_counters = static_cast<int64_t>(P->n_pool[0]) + 2 + (P->sparse ? 0 : cells);
     return P;
 }
 
@@ -275,15 +270,8 @@ std::unique_ptr<scg_plan> compile_paired_combo(const char* constant1, int revers
     int len2 = scg::pool_length(pool2, n2);
     P->ht1 = scg::parse_template(constant1, reverse1 ? 1 : 0);
     P->ht2 = scg::parse_template(constant2, reverse2 ? 1 : 0);
-    auto check = [](const scg::HostTemplate& ht, int plen) {   // SimpleSingleMatch.hpp:75-83
-        if (ht.t.nreg != 1) throw Error(SCG_ERR_INVALID, "expected one variable region in the constant template");
-        if (ht.t.flen[0] != plen) {
-            throw Error(SCG_ERR_INVALID, "length of barcode_pool sequences (" + std::to_string(plen) +
-                        ") should be the same as the barcode_pool region (" + std::to_string(ht.t.flen[0]) + ")");
-        }
-    };
-    check(P->ht1, len1);
-    check(P->ht2, len2);
+    check_single_match(P->ht1, len1);
+    check_single_match(P->ht2, len2);
     if (mismatches1 < 0 || mismatches2 < 0) throw Error(SCG_ERR_INVALID, "negative number of mismatches");
     const int cls = std::max(key_class(len1), key_class(len2));
     P->htab[0] = build_index_class(cls, pool1, n1, len1, mismatches1);     // values = pool indices; duplicates => error
@@ -306,19 +294,56 @@ std::unique_ptr<scg_plan> compile_paired_combo(const char* constant1, int revers
     return P;
 }
 
+// ---- kernel arguments: each struct is built in one place, from a value-initialised one ----
+
+// Counters at `base` and nothing else: no replicas, no index or combination stream, no hot slots.
+ScgCounters plain_counters(int32_t* base) {
+    ScgCounters c = ScgCounters();
+    c.base = base;
+    return c;
+}
+
 ScgCounters plan_counters(const scg_plan* P) {
-    ScgCounters c;
+    ScgCounters c = plain_counters(P->counters);
     if (P->replica_shift > 0) {
         c.base = P->replicas.as<int32_t>();
         c.replica_shift = static_cast<uint32_t>(P->replica_shift);
         c.replica_mask = (1u << P->replica_shift) - 1u;
-    } else {
-        c.base = P->counters; c.replica_mask = 0; c.replica_shift = 0;
     }
-    c.unit_index = nullptr;
-    c.unit_pair = nullptr;
     c.hot = P->hot.p ? P->hot.as<int32_t>() : nullptr;
     return c;
+}
+
+// The template of the plan searched in `index`; the random-barcode paths, which have no library, pass ScgIndex().
+ScgSingleParams single_params(const scg_plan* P, const ScgIndex& index) {
+    ScgSingleParams sp = ScgSingleParams();
+    sp.scan = P->scan1;
+    sp.tmpl = P->d_tmpl1.as<ScgTemplate>();
+    sp.index = index;
+    sp.max_mm = P->max_mm1; sp.use_first = P->use_first;
+    sp.fwd = P->ht1.fwd; sp.rev = P->ht1.rev;
+    return sp;
+}
+
+// The combination search over the plan's two pools; the second pass of include.invalid=TRUE overrides n_pool,
+// only_if_negative and keep_first.
+ScgComboParams combo_params(const scg_plan* P) {
+    ScgComboParams cp = ScgComboParams();
+    cp.scan = P->scan1;
+    cp.tmpl = P->d_tmpl1.as<ScgTemplate>();
+    cp.index[0] = P->tab[0].view; cp.index[1] = P->tab[1].view;
+    cp.n_pool[0] = P->n_pool[0]; cp.n_pool[1] = P->n_pool[1];
+    cp.max_mm = P->max_mm1; cp.use_first = P->use_first;
+    cp.fwd = P->ht1.fwd; cp.rev = P->ht1.rev;
+    return cp;
+}
+
+// The index stream of the batch of n reads about to run on `stream`: the barcode index per read, for the tally
+// (ScgCounters::unit_index).  One buffer per stream: batches on different streams may be in flight together.
+int32_t* index_stream(scg_plan* P, hipStream_t stream, int64_t n) {
+    DevBuf& buf = P->unit_index[stream];
+    buf.ensure(static_cast<size_t>(n) * sizeof(int32_t));
+    return buf.as<int32_t>();
 }
 
 // ---- sparse mode: combination streams ----
@@ -371,6 +396,13 @@ void retire_all_pairs(scg_plan* P) {
     for (auto& kv : P->pair_stream) retire_pairs(P, kv.first, kv.second);
 }
 
+// A reset of the plan: the batches in flight are let finish and their runs dropped.
+void drop_pending_pairs(scg_plan* P) {
+    for (auto& kv : P->pair_stream) {
+        if (kv.second.pending) { HIP_CHECK(hipEventSynchronize(kv.second.done)); kv.second.pending = 0; }
+    }
+}
+
 // Tally mode pays off when the library is large enough that block-level aggregation finds no repeats
 // (small libraries are served by the replicas) and small enough for a few LDS passes, on batches
 // large enough to amortise the second kernel.  SCG_TALLY=0/1 overrides (measurement aid).
@@ -392,30 +424,15 @@ void fold_replicas(scg_plan* P, hipStream_t stream) {
 // and counts (uid1, uid2) cells behind the two unused diagnostics slots: [n_pool][2][n_uid1 x n_uid2].
 void launch_batch_se_diag(scg_plan* P, const ScgReads& R, int64_t n, hipStream_t stream) {
     scg_plan::Timer timer(P, stream);
-    DevBuf& buf = P->unit_index[stream];
-    buf.ensure(static_cast<size_t>(n) * sizeof(int32_t));
-    ScgSingleParams sp;
-    sp.scan = P->scan1;
-    sp.tmpl = P->d_tmpl1.as<ScgTemplate>();
-    sp.index = P->tab_combined.view;
-    sp.max_mm = P->max_mm1; sp.use_first = P->use_first;
-    sp.fwd = P->ht1.fwd; sp.rev = P->ht1.rev;
-    ScgCounters c1;
-    c1.base = P->counters; c1.replica_mask = 0; c1.replica_shift = 0; c1.hot = nullptr; c1.unit_pair = nullptr;
-    c1.unit_index = buf.as<int32_t>();
-    HIP_CHECK(scg::launch_single(sp, P->ht1.t.len, R, n, c1, P->error_flag.as<int32_t>(), stream));
+    ScgCounters c1 = plain_counters(P->counters);
+    c1.unit_index = index_stream(P, stream, n);
+    HIP_CHECK(scg::launch_single(single_params(P, P->tab_combined.view), P->ht1.t.len, R, n, c1, P->error_flag.as<int32_t>(), stream));
     HIP_CHECK(scg::launch_tally(c1.unit_index, n, P->counters, P->n_pool[0], stream));
-    ScgComboParams cp;
-    cp.scan = P->scan1;
-    cp.tmpl = P->d_tmpl1.as<ScgTemplate>();
-    cp.index[0] = P->tab[0].view; cp.index[1] = P->tab[1].view;
+    ScgComboParams cp = combo_params(P);
     cp.n_pool[0] = static_cast<int32_t>(P->first1.size()); cp.n_pool[1] = static_cast<int32_t>(P->first2.size());
-    cp.max_mm = P->max_mm1; cp.use_first = P->use_first;
-    cp.fwd = P->ht1.fwd; cp.rev = P->ht1.rev;
-    cp.only_if_negative = c1.unit_index; cp.keep_first = 1; cp.pad = 0;
-    ScgCounters c2;
-    c2.base = P->counters + P->n_pool[0] + 2; c2.replica_mask = 0; c2.replica_shift = 0; c2.unit_index = nullptr; c2.hot = nullptr;
-    c2.unit_pair = P->sparse ? begin_pairs(P, stream, n) : nullptr;
+    cp.only_if_negative = c1.unit_index; cp.keep_first = 1;
+    ScgCounters c2 = plain_counters(P->counters + P->n_pool[0] + 2);
+    if (P->sparse) c2.unit_pair = begin_pairs(P, stream, n);
     HIP_CHECK(scg::launch_combo(cp, P->ht1.t.len, R, n, c2, P->error_flag.as<int32_t>(), stream));
     timer.stop();
     if (P->sparse) finish_pairs(P, stream, n);
@@ -424,12 +441,13 @@ void launch_batch_se_diag(scg_plan* P, const ScgReads& R, int64_t n, hipStream_t
 
 // ---- countRandomBarcodes plans: the tally in HBM (scg_random.hip) ----
 
-// kaori::RandomBarcodeSingleEnd (handlers/RandomBarcodeSingleEnd.hpp:86-181) with the argument checks of the file entry
-// (scg_count_random_barcodes), in its order.  The key is the FIRST forward region on both strands, like the reference.
-std::unique_ptr<scg_plan> compile_random(const char* constant, int strand, int mismatches, int use_first) {
+// kaori::RandomBarcodeSingleEnd (handlers/RandomBarcodeSingleEnd.hpp:86-181): the template and every argument check of
+// countRandomBarcodes, for the file entry (count_random_file, which tallies on the host) and for the plans below.  A plan
+// of the SINGLE kind without a library or counters: the template is located by launch_random, which reads no index.
+std::unique_ptr<scg_plan> compile_random_template(const char* constant, int strand, int mismatches, int use_first) {
     if (!constant) throw Error(SCG_ERR_INVALID, "null argument");
     std::unique_ptr<scg_plan> P(new scg_plan);
-    P->kind = scg_plan::RANDOM;
+    P->kind = scg_plan::SINGLE;
     P->ht1 = scg::parse_template(constant, strand);
     const ScgTemplate& t = P->ht1.t;
     if (t.nreg < 1) throw Error(SCG_ERR_INVALID, "expected one variable region in the constant template");
@@ -439,9 +457,16 @@ std::unique_ptr<scg_plan> compile_random(const char* constant, int strand, int m
     P->max_mm1 = mismatches;
     P->use_first = use_first != 0;
     P->n_counters = 0;
+    return P;
+}
+
+// The same with the tally in HBM.  The key is the FIRST forward region on both strands, like the reference.
+std::unique_ptr<scg_plan> compile_random(const char* constant, int strand, int mismatches, int use_first) {
+    std::unique_ptr<scg_plan> P = compile_random_template(constant, strand, mismatches, use_first);
+    P->kind = scg_plan::RANDOM;
     P->rnd.reset(new RandomTally);
-    P->rnd->vstart = t.fstart[0];
-    P->rnd->vlen = t.flen[0];
+    P->rnd->vstart = P->ht1.t.fstart[0];
+    P->rnd->vlen = P->ht1.t.flen[0];
     // Test hook, read here only: hashed tags keep this many hash bits (default and maximum 61), so that tests can make
     // tags collide and exhaust the rounds.  Results never depend on it unless the rounds run out, which read-out reports.
     if (const char* e = std::getenv("SCG_TEST_RANDOM_TAG_BITS")) {
@@ -470,16 +495,6 @@ void random_order(RandomTally& T, hipStream_t stream) {
 void random_done(RandomTally& T, hipStream_t stream) {
     HIP_CHECK(hipEventRecord(T.last, stream));
     T.has_last = true;
-}
-
-ScgSingleParams random_params(const scg_plan* P) {
-    ScgSingleParams sp;
-    sp.scan = P->scan1;
-    sp.tmpl = P->d_tmpl1.as<ScgTemplate>();
-    std::memset(&sp.index, 0, sizeof(sp.index));
-    sp.max_mm = P->max_mm1; sp.use_first = P->use_first;
-    sp.fwd = P->ht1.fwd; sp.rev = P->ht1.rev;
-    return sp;
 }
 
 // Keeps occupancy <= capacity / 2 for the batch of n reads about to be counted on `stream`.  The bound is the last
@@ -540,7 +555,7 @@ void launch_batch_random(scg_plan* P, const ScgReads& R, int64_t n, hipStream_t 
         // a staged kernel that meets an oversize read flags it and leaves its hit unwritten: -1 there
         HIP_CHECK(hipMemsetAsync(s.hits.p, 0xFF, bytes, stream));
         HIP_CHECK(hipMemsetAsync(s.lens.p, 0, SCG_RANDOM_ROUNDS * sizeof(int32_t), stream));
-        HIP_CHECK(scg::launch_random(random_params(P), P->ht1.t.len, R, n, s.hits.as<int32_t>(), P->error_flag.as<int32_t>(), stream));
+        HIP_CHECK(scg::launch_random(single_params(P, ScgIndex()), P->ht1.t.len, R, n, s.hits.as<int32_t>(), P->error_flag.as<int32_t>(), stream));
         const scg::ScgRandomTable view = T.view();
         HIP_CHECK(scg::launch_random_insert(view, R, n, s.hits.as<int32_t>(), s.slots.as<int32_t>(), P->total, stream));
         HIP_CHECK(scg::launch_random_verify_rounds(view, R, n, s.hits.as<int32_t>(), s.slots.as<int32_t>(), s.list_a.as<int32_t>(),
@@ -655,89 +670,45 @@ void read_random(scg_plan* P, hipStream_t stream, char** sequences_out, int32_t*
         return static_cast<int32_t>(c);
     };
     const size_t K = np + nh;
-    char* so = static_cast<char*>(std::malloc(K * stride + 1));
-    int32_t* fo = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * (K + 1)));
-    if (!so || !fo) { std::free(so); std::free(fo); throw std::bad_alloc(); }
-    try {
-        size_t a = 0, b = 0;
-        for (size_t k = 0; k < K; ++k) {
-            const bool take_packed = b == nh ||
-                (a < np && std::memcmp(pbytes.data() + a * stride, hbytes.data() + horder[b] * vlen, static_cast<size_t>(vlen)) < 0);
-            if (take_packed) {
-                std::memcpy(so + k * stride, pbytes.data() + a * stride, stride);
-                fo[k] = narrow(pc[a++]);
-            } else {
-                std::memcpy(so + k * stride, hbytes.data() + horder[b] * vlen, static_cast<size_t>(vlen));
-                so[k * stride + vlen] = 0;
-                fo[k] = narrow(hc[horder[b++]]);
-            }
+    OutPair<char, int32_t> out(K * stride + 1, K + 1);
+    char* so = out.a;
+    size_t a = 0, b = 0;
+    for (size_t k = 0; k < K; ++k) {
+        const bool take_packed = b == nh ||
+            (a < np && std::memcmp(pbytes.data() + a * stride, hbytes.data() + horder[b] * vlen, static_cast<size_t>(vlen)) < 0);
+        if (take_packed) {
+            std::memcpy(so + k * stride, pbytes.data() + a * stride, stride);
+            out.b[k] = narrow(pc[a++]);
+        } else {
+            std::memcpy(so + k * stride, hbytes.data() + horder[b] * vlen, static_cast<size_t>(vlen));
+            so[k * stride + vlen] = 0;
+            out.b[k] = narrow(hc[horder[b++]]);
         }
-    } catch (...) {
-        std::free(so); std::free(fo);
-        throw;
     }
-    *sequences_out = so; *freq_out = fo; *k_out = static_cast<int64_t>(K); *length_out = vlen;
+    out.release(sequences_out, freq_out);
+    *k_out = static_cast<int64_t>(K); *length_out = vlen;
 }
 
+// One batch of a single-end plan.  Combinations beyond the dense limit travel as a key stream (sparse mode); otherwise
+// the staged kernels can write an index stream for the tally (use_tally), and what remains counts with atomics on the
+// replicas, folded behind the kernel.
 void launch_batch(scg_plan* P, const ScgReads& R, int64_t n, hipStream_t stream) {
     if (P->kind == scg_plan::RANDOM) { launch_batch_random(P, R, n, stream); return; }
     if (P->kind == scg_plan::DUAL_SE_DIAG) { launch_batch_se_diag(P, R, n, stream); return; }
     scg_plan::Timer timer(P, stream);
+    ScgCounters counts = plan_counters(P);
+    const bool tally = !P->sparse && use_tally(P, n) && scg::staged_takes(R.max_len) && !general_only(P);
+    if (P->sparse) counts.unit_pair = begin_pairs(P, stream, n);
+    else if (tally) counts.unit_index = index_stream(P, stream, n);
     if (P->kind == scg_plan::SINGLE) {
-        ScgSingleParams sp;
-        sp.scan = P->scan1;
-        sp.tmpl = P->d_tmpl1.as<ScgTemplate>();
-        sp.index = P->tab[0].view;
-        sp.max_mm = P->max_mm1; sp.use_first = P->use_first;
-        sp.fwd = P->ht1.fwd; sp.rev = P->ht1.rev;
-            ScgCounters counts = plan_counters(P);
-        const bool tally = use_tally(P, n) && R.max_len > 0 && R.max_len <= 320 && !general_only(P);
-        if (tally) {
-            DevBuf& buf = P->unit_index[stream];              // batches on different streams may be in flight together
-            buf.ensure(static_cast<size_t>(n) * sizeof(int32_t));
-            counts.unit_index = buf.as<int32_t>();
-        }
-        HIP_CHECK(scg::launch_single(sp, P->ht1.t.len, R, n, counts, P->error_flag.as<int32_t>(), stream));
-        if (tally) {
-            timer.stop();                                      // kernel statistics cover the counting kernel, as in rocprof
-            HIP_CHECK(scg::launch_tally(counts.unit_index, n, P->counters, P->n_counters, stream));
-            P->total += n;
-            return;
-        }
+        HIP_CHECK(scg::launch_single(single_params(P, P->tab[0].view), P->ht1.t.len, R, n, counts, P->error_flag.as<int32_t>(), stream));
     } else {
-        ScgComboParams cp;
-        cp.scan = P->scan1;
-        cp.tmpl = P->d_tmpl1.as<ScgTemplate>();
-        cp.index[0] = P->tab[0].view; cp.index[1] = P->tab[1].view;
-        cp.n_pool[0] = P->n_pool[0]; cp.n_pool[1] = P->n_pool[1];
-        cp.max_mm = P->max_mm1; cp.use_first = P->use_first;
-        cp.fwd = P->ht1.fwd; cp.rev = P->ht1.rev;
-        cp.only_if_negative = nullptr; cp.keep_first = 0; cp.pad = 0;
-        ScgCounters counts = plan_counters(P);
-        if (P->sparse) {
-            counts.unit_pair = begin_pairs(P, stream, n);
-            HIP_CHECK(scg::launch_combo(cp, P->ht1.t.len, R, n, counts, P->error_flag.as<int32_t>(), stream));
-            timer.stop();
-            finish_pairs(P, stream, n);
-            P->total += n;
-            return;
-        }
-        const bool tally = use_tally(P, n) && R.max_len > 0 && R.max_len <= 320 && !general_only(P);
-        if (tally) {
-            DevBuf& buf = P->unit_index[stream];
-            buf.ensure(static_cast<size_t>(n) * sizeof(int32_t));
-            counts.unit_index = buf.as<int32_t>();
-        }
-        HIP_CHECK(scg::launch_combo(cp, P->ht1.t.len, R, n, counts, P->error_flag.as<int32_t>(), stream));
-        if (tally) {
-            timer.stop();
-            HIP_CHECK(scg::launch_tally(counts.unit_index, n, P->counters, P->n_counters, stream));
-            P->total += n;
-            return;
-        }
+        HIP_CHECK(scg::launch_combo(combo_params(P), P->ht1.t.len, R, n, counts, P->error_flag.as<int32_t>(), stream));
     }
-    timer.stop();
-    fold_replicas(P, stream);
+    timer.stop();                                          // kernel statistics cover the counting kernel, as in rocprof
+    if (P->sparse) finish_pairs(P, stream, n);
+    else if (tally) HIP_CHECK(scg::launch_tally(counts.unit_index, n, P->counters, P->n_counters, stream));
+    else fold_replicas(P, stream);
     P->total += n;
 }
 
@@ -761,7 +732,7 @@ ScgScan searched_strand_first(const ScgScan& t, bool reverse) {
 
 void launch_batch_paired(scg_plan* P, const ScgReads& R1, const ScgReads& R2, int64_t n, hipStream_t stream) {
     scg_plan::Timer timer(P, stream);
-    ScgDualParams dp;
+    ScgDualParams dp = ScgDualParams();
     dp.scan1 = searched_strand_first(P->scan1, P->rev1); dp.scan2 = searched_strand_first(P->scan2, P->rev2);
     dp.tmpl1 = P->d_tmpl1.as<ScgTemplate>(); dp.tmpl2 = P->d_tmpl2.as<ScgTemplate>();
     dp.index1 = P->tab[0].view; dp.index2 = P->tab[1].view; dp.pairs = P->pairs.view;
@@ -772,7 +743,7 @@ void launch_batch_paired(scg_plan* P, const ScgReads& R1, const ScgReads& R2, in
     ScgCounters counts = plan_counters(P);
     if (P->sparse) counts.unit_pair = begin_pairs(P, stream, n);      // (the invalid / all combinations of the diagnostics passes)
     const int lo_len = std::min(R1.max_len, R2.max_len), hi_len = std::max(R1.max_len, R2.max_len);
-    const bool staged = lo_len > 0 && hi_len <= 320 && !general_only(P);
+    const bool staged = scg::staged_takes(lo_len) && scg::staged_takes(hi_len) && !general_only(P);
     const int tmpl_len = std::max(P->ht1.t.len, P->ht2.t.len);
     dp.overflow = nullptr;
     if (staged && P->diagnostics != 2 && n < INT32_MAX) {
@@ -783,10 +754,8 @@ void launch_batch_paired(scg_plan* P, const ScgReads& R1, const ScgReads& R2, in
     if (P->diagnostics == 1 && staged) {
         // include.invalid=TRUE in two lean passes: valid pairs as an index stream (tallied), then the mate-by-mate
         // search on the pairs that found none
-        DevBuf& buf = P->unit_index[stream];
-        buf.ensure(static_cast<size_t>(n) * sizeof(int32_t));
         ScgCounters c1 = counts;
-        c1.unit_index = buf.as<int32_t>();
+        c1.unit_index = index_stream(P, stream, n);
         c1.unit_pair = nullptr;
         dp.diagnostics = 0;
         HIP_CHECK(scg::launch_dual(dp, tmpl_len, R1, R2, n, c1, P->error_flag.as<int32_t>(), stream));
@@ -802,11 +771,7 @@ void launch_batch_paired(scg_plan* P, const ScgReads& R1, const ScgReads& R2, in
         return;
     }
     const bool tally = use_tally(P, n) && staged;
-    if (tally) {
-        DevBuf& buf = P->unit_index[stream];
-        buf.ensure(static_cast<size_t>(n) * sizeof(int32_t));
-        counts.unit_index = buf.as<int32_t>();
-    }
+    if (tally) counts.unit_index = index_stream(P, stream, n);
     HIP_CHECK(scg::launch_dual(dp, tmpl_len, R1, R2, n, counts, P->error_flag.as<int32_t>(), stream));
     timer.stop();
     if (P->sparse) finish_pairs(P, stream, n);

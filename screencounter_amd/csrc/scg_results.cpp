@@ -1,5 +1,6 @@
 // scg_results.cpp -- what a file-level call has around its pipelines: the devices it may use, the plans on them (PlanSet),
-// the scheduling of many files over them, and the shaping of counters into the reference's outputs.
+// the scheduling of many files over them, and the shaping of counters into the reference's outputs: one reader per kind
+// of result (result_counts, result_combinations, result_diagnostics), shared by the plan, one-file and many-files entries.
 #include "scg_internal.hpp"
 
 namespace scgapi {
@@ -10,9 +11,7 @@ void reset_plan(scg_plan* P) {
     if (P->replica_shift > 0) HIP_CHECK(hipMemset(P->replicas.p, 0, P->replicas.bytes));
     HIP_CHECK(hipMemset(P->error_flag.p, 0, sizeof(int32_t)));    // (what set it is recounted, or belongs to the previous file)
     HIP_CHECK(hipStreamSynchronize(nullptr));               // (the fills are only enqueued: scg_plan::upload)
-    for (auto& kv : P->pair_stream) {                       // (sparse mode: batches in flight are let finish and dropped)
-        if (kv.second.pending) { HIP_CHECK(hipEventSynchronize(kv.second.done)); kv.second.pending = 0; }
-    }
+    drop_pending_pairs(P);                                  // (sparse mode: batches in flight are let finish and dropped)
     P->sparse_counts.clear();
     P->total = 0;
 }
@@ -185,20 +184,19 @@ void schedule_paired(int32_t n_files, const PlanSet& set, const char* const* pat
 void combo_compact(const int32_t* cells, int32_t n0, int32_t n1, int32_t** indices_out, int32_t** freq_out, int64_t* k_out) {
     int64_t total = static_cast<int64_t>(n0) * n1, k = 0;
     for (int64_t c = 0; c < total; ++c) k += cells[c] != 0;
-    int32_t* idx = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * static_cast<size_t>(2 * k + 1)));
-    int32_t* freq = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * static_cast<size_t>(k + 1)));
-    if (!idx || !freq) { std::free(idx); std::free(freq); throw std::bad_alloc(); }
+    OutPair<int32_t, int32_t> out(static_cast<size_t>(2 * k + 1), static_cast<size_t>(k + 1));
     int64_t j = 0;
     // cell order = (first, second) lexicographic order = the reference's sorted column order
     for (int64_t c = 0; c < total; ++c) {
         if (cells[c]) {
-            idx[2 * j] = static_cast<int32_t>(c / n1);
-            idx[2 * j + 1] = static_cast<int32_t>(c % n1);
-            freq[j] = cells[c];
+            out.a[2 * j] = static_cast<int32_t>(c / n1);
+            out.a[2 * j + 1] = static_cast<int32_t>(c % n1);
+            out.b[j] = cells[c];
             ++j;
         }
     }
-    *indices_out = idx; *freq_out = freq; *k_out = k;
+    out.release(indices_out, freq_out);
+    *k_out = k;
 }
 
 // Sparse mode: (first << 32 | second) -> count, as the reference's sorted run-length form (src/utils.h:14-45).
@@ -206,16 +204,15 @@ void combos_from_sparse(const std::unordered_map<uint64_t, int64_t>& m, int32_t*
     std::vector<std::pair<uint64_t, int64_t> > rows(m.begin(), m.end());
     std::sort(rows.begin(), rows.end());                    // key order = (first, second) order
     const size_t k = rows.size();
-    int32_t* idx = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * (2 * k + 1)));
-    int32_t* freq = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * (k + 1)));
-    if (!idx || !freq) { std::free(idx); std::free(freq); throw std::bad_alloc(); }
+    OutPair<int32_t, int32_t> out(2 * k + 1, k + 1);
     for (size_t j = 0; j < k; ++j) {
-        if (rows[j].second > static_cast<int64_t>(INT32_MAX)) { std::free(idx); std::free(freq); throw Error(SCG_ERR_INVALID, "a count exceeds the 32-bit range of the count vectors"); }
-        idx[2 * j] = static_cast<int32_t>(rows[j].first >> 32);
-        idx[2 * j + 1] = static_cast<int32_t>(rows[j].first & 0xFFFFFFFFu);
-        freq[j] = static_cast<int32_t>(rows[j].second);
+        if (rows[j].second > static_cast<int64_t>(INT32_MAX)) throw Error(SCG_ERR_INVALID, "a count exceeds the 32-bit range of the count vectors");
+        out.a[2 * j] = static_cast<int32_t>(rows[j].first >> 32);
+        out.a[2 * j + 1] = static_cast<int32_t>(rows[j].first & 0xFFFFFFFFu);
+        out.b[j] = static_cast<int32_t>(rows[j].second);
     }
-    *indices_out = idx; *freq_out = freq; *k_out = static_cast<int64_t>(k);
+    out.release(indices_out, freq_out);
+    *k_out = static_cast<int64_t>(k);
 }
 
 // [n_pool valid][b1][b2][uid1 x uid2] -> the reference's outputs: invalid combinations by first pool
@@ -257,12 +254,8 @@ void diagnostics_from_counters(const scg_plan* P, const std::vector<int32_t>& al
             freq.push_back(found[i].second);
         }
     }
-    int32_t* oi = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * (idx.size() + 1)));
-    int32_t* of = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * (freq.size() + 1)));
-    if (!oi || !of) { std::free(oi); std::free(of); throw std::bad_alloc(); }
-    std::copy(idx.begin(), idx.end(), oi);
-    std::copy(freq.begin(), freq.end(), of);
-    *idx_out = oi; *freq_out = of; *k_out = static_cast<int64_t>(freq.size());
+    vectors_out(idx, 1, freq, 1, idx_out, freq_out);
+    *k_out = static_cast<int64_t>(freq.size());
 }
 
 PlanSet::PlanSet(std::unique_ptr<scg_plan> compiled, const std::vector<int>& devices) {
@@ -275,10 +268,6 @@ std::vector<scg_plan*> PlanSet::all() const {
     for (auto& p : plans) v.push_back(p.get());
     return v;
 }
-int64_t PlanSet::total() const { return total_of(all()); }
-void PlanSet::read(int32_t* counts_out) const { read_plans(all(), counts_out); }
-void PlanSet::reset() const { for (auto& p : plans) reset_plan(p.get()); }
-std::unordered_map<uint64_t, int64_t> PlanSet::sparse_merged() const { return scgapi::sparse_merged(all()); }
 
 // ---- one counted input -> the outputs of its entry point ------------------------------------------------------
 int64_t total_of(const std::vector<scg_plan*>& plans) {
@@ -322,6 +311,16 @@ std::unordered_map<uint64_t, int64_t> sparse_merged(const std::vector<scg_plan*>
 void result_counts(const std::vector<scg_plan*>& plans, int32_t* counts_out, int32_t* total_out) {
     read_plans(plans, counts_out);
     *total_out = narrow_total(total_of(plans));
+}
+
+void result_combinations(const std::vector<scg_plan*>& plans, int32_t** idx_out, int32_t** freq_out, int64_t* k_out, int32_t* total_out) {
+    const scg_plan* P = plans[0];
+    std::vector<int32_t> cells(static_cast<size_t>(P->n_counters) + 1);
+    read_plans(plans, cells.data());
+    const int32_t total = total_out ? narrow_total(total_of(plans)) : 0;      // (before anything is allocated for the caller)
+    if (P->sparse) combos_from_sparse(sparse_merged(plans), idx_out, freq_out, k_out);
+    else combo_compact(cells.data(), P->n_pool[0], P->n_pool[1], idx_out, freq_out, k_out);
+    if (total_out) *total_out = total;
 }
 
 void result_diagnostics(const std::vector<scg_plan*>& plans, int32_t* counts_out, int32_t** idx_out, int32_t** freq_out, int64_t* k_out,
