@@ -273,6 +273,23 @@ int scg_count_combo_barcodes_paired_files(const char* const* paths1, const char*
                                           int32_t* totals_out, int32_t* barcode1_only_out, int32_t* barcode2_only_out,
                                           char* err, size_t errcap);
 
+/* matrixOfRandomBarcodes (R/countRandomBarcodes.R:84-104): the files' tallies as one matrix in compressed-column form.
+ * Rows are the byte-wise sorted union of the keys that at least one file counted: *sequences_out holds *k_out
+ * NUL-terminated strings of *length_out characters (stride *length_out + 1).  Column f holds file f's non-zero counts:
+ * entries (*col_ptr_out)[f] .. (*col_ptr_out)[f + 1] - 1 of *rows_out (0-based rows, ascending) and *freq_out, exactly what
+ * scg_count_random_barcodes returns for paths[f] alone; totals_out[f] is its number of reads.  *col_ptr_out has
+ * n_files + 1 entries.  Release the four arrays with scg_free.  Every device of the call keeps one tally in HBM for all
+ * the files it takes (as the plans of scg_plan_random do for their batches): key bytes are sorted and copied back once
+ * per device, a file leaves the device as (row, count) pairs.  A null pointer or n_files < 0 is SCG_ERR_INVALID; the
+ * first file's reader and then the argument errors of scg_count_random_barcodes come before any device work;
+ * n_files == 0 succeeds with K = 0 (and four arrays to release).  When any file fails, the call fails with the error of
+ * the lowest-numbered failing file -- the message scg_count_random_barcodes gives for it -- and hands nothing out. */
+int scg_count_random_barcodes_files(const char* const* paths, int32_t n_files,
+                                    const char* constant, int strand, int mismatches, int use_first, int nthreads,
+                                    char** sequences_out, int64_t* k_out, int32_t* length_out,
+                                    int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out,
+                                    int32_t* totals_out, char* err, size_t errcap);
+
 /* matchBarcodes.  Replaces src/match_barcodes.cpp:6-37.  index_out[i] is the 0-based index of the
  * unique best choice within `substitutions` mismatches or -1 (R: NA); mismatches_out likewise. */
 int scg_match_barcodes(const char* const* sequences, int32_t n_sequences,

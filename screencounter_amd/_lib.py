@@ -80,6 +80,9 @@ SIGNATURES = {
                                                         c_str_p, C.c_char_p, C.c_int, C.c_int, c_str_p, C.c_int32, C.c_int32,
                                                         C.c_int, C.c_int, C.c_int, C.POINTER(i32_p), C.POINTER(i32_p), i64_p,
                                                         i32_p, i32_p, i32_p, C.c_char_p, C.c_size_t]),
+    "scg_count_random_barcodes_files": (C.c_int, [c_str_p, C.c_int32, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.POINTER(C.c_void_p), i64_p, i32_p, C.POINTER(i64_p), C.POINTER(i32_p), C.POINTER(i32_p),
+                                                  i32_p, C.c_char_p, C.c_size_t]),
     "scg_fastq_text_windows": (C.c_int, [C.c_char_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p), i64_p, C.POINTER(C.c_void_p), i64_p,
                                          C.c_char_p, C.c_char_p, C.c_size_t]),
     "scg_fastq_scan_windows": (C.c_int, [C.c_char_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), i64_p, i64_p,

@@ -338,6 +338,41 @@ def count_random_barcodes(path: str, constant: str, strand: int, mismatches: int
     return (seqs, freq), int(total.value)
 
 
+def count_random_barcodes_files(paths: Sequence[str], constant: str, strand: int, mismatches: int, use_first: bool, nthreads: int = 1,
+                                devices=None):
+    """scg_count_random_barcodes_files: every file of matrixOfRandomBarcodes in one native call, tallied in HBM
+    -> (keys list[str] sorted: the union over the files, matrix int32[K, n_files] dense as R builds it
+    (R/countRandomBarcodes.R:87-92), totals int32[n_files])."""
+    L = _lib.load()
+    n = len(paths)
+    seq_p = C.c_void_p()
+    colptr_p, rows_p, freq_p = _lib.i64_p(), _lib.i32_p(), _lib.i32_p()
+    k, vlen = C.c_int64(0), C.c_int32(0)
+    totals = np.zeros(max(n, 1), dtype=np.int32)
+    err = errbuf()
+    farr, _fk = cstr_array([os.fspath(x) for x in paths])
+    with _devices_env(devices):
+        check(L.scg_count_random_barcodes_files(farr, n, constant.encode(), int(strand), int(mismatches), int(bool(use_first)), int(nthreads),
+                                                C.byref(seq_p), C.byref(k), C.byref(vlen), C.byref(colptr_p), C.byref(rows_p), C.byref(freq_p),
+                                                totals.ctypes.data_as(_lib.i32_p), err, _lib.ERRCAP), err)
+    K, W = int(k.value), int(vlen.value)
+    try:
+        blob = C.string_at(seq_p, K * (W + 1)) if K else b""
+        keys = [blob[i * (W + 1): i * (W + 1) + W].decode("latin-1") for i in range(K)]
+        colptr = np.ctypeslib.as_array(colptr_p, shape=(n + 1,)).copy()
+        nnz = int(colptr[n])
+        rows = np.ctypeslib.as_array(rows_p, shape=(max(nnz, 1),))[:nnz].copy()
+        freq = np.ctypeslib.as_array(freq_p, shape=(max(nnz, 1),))[:nnz].copy()
+    finally:
+        L.scg_free(seq_p)
+        L.scg_free(colptr_p)
+        L.scg_free(rows_p)
+        L.scg_free(freq_p)
+    matrix = np.zeros((K, n), dtype=np.int32)
+    matrix[rows, np.repeat(np.arange(n), np.diff(colptr))] = freq
+    return keys, matrix, totals[:n].copy()
+
+
 def count_dual_barcodes_single_end(path: str, constant: str, pools: Sequence[Sequence[str]], strand: int, mismatches: int,
                                    use_first: bool, diagnostics: bool = False, nthreads: int = 1):
     """src/count_dual_barcodes_single_end.cpp:53-87 -> (counts int32[n combinations], total), or with diagnostics=True

@@ -566,9 +566,9 @@ int scg_count_dual_barcodes_files(const char* const* paths1, const char* constan
 
 // The four entries below check their arguments -- the template and the pools are compiled, host work only -- before any
 // file is opened and any device is touched; then every device gets its plan and takes the files one at a time.  In all
-// seven many-files entries a plan starts every file from reset_plan (counters, sparse combinations, runs in flight, the
-// oversize-read flag), and a file's outputs are read by the function its one-file entry reads them with (result_counts,
-// result_combinations, result_diagnostics).
+// seven many-files entries with a library a plan starts every file from reset_plan (counters, sparse combinations, runs in
+// flight, the oversize-read flag), and a file's outputs are read by the function its one-file entry reads them with
+// (result_counts, result_combinations, result_diagnostics).
 
 int scg_count_dual_barcodes_diagnostics_files(const char* const* paths1, const char* constant1, int reverse1, int mismatches1, const char* const* pool1,
                                               const char* const* paths2, const char* constant2, int reverse2, int mismatches2, const char* const* pool2,
@@ -662,6 +662,43 @@ int scg_count_combo_barcodes_paired_files(const char* const* paths1, const char*
                                    &barcode1_only_out[f], &barcode2_only_out[f]);
             });
         });
+    });
+}
+
+// matrixOfRandomBarcodes.  Every device keeps ONE random-barcode table (files mode) for all the files it
+// takes: a file starts from the soft reset of reset_plan, runs the ladder of every other single-end entry, and leaves as
+// (row id, count) pairs (random_harvest, which makes the checks of the plan read-out first); the keys leave each device
+// once, when all files are done.  Nothing is handed out before the whole matrix stands.
+int scg_count_random_barcodes_files(const char* const* paths, int32_t n_files, const char* constant, int strand, int mismatches, int use_first,
+                                    int nthreads, char** sequences_out, int64_t* k_out, int32_t* length_out, int64_t** col_ptr_out,
+                                    int32_t** rows_out, int32_t** freq_out, int32_t* totals_out, char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (n_files < 0 || !constant || !sequences_out || !k_out || !length_out || !col_ptr_out || !rows_out || !freq_out ||
+            (n_files > 0 && (!paths || !totals_out))) {
+            throw Error(SCG_ERR_INVALID, "null argument");
+        }
+        *sequences_out = nullptr; *col_ptr_out = nullptr; *rows_out = nullptr; *freq_out = nullptr; *k_out = 0; *length_out = 0;
+        for (int32_t f = 0; f < n_files; ++f) if (!paths[f]) throw Error(SCG_ERR_INVALID, "null argument");
+        if (n_files == 0) {                                            // an empty matrix, with arrays to release like any other
+            OutPair<char, int64_t> head(1, 1);
+            OutPair<int32_t, int32_t> body(1, 1);
+            head.a[0] = 0; head.b[0] = 0;
+            head.release(sequences_out, col_ptr_out);
+            body.release(rows_out, freq_out);
+            return;
+        }
+        { scg::FastqStream probe(paths[0]); }                          // the first file's reader comes before the argument checks, as in a loop over files
+        std::unique_ptr<scg_plan> compiled = compile_random(constant, strand, mismatches, use_first);
+        compiled->rnd->files = true;
+        PlanSet set(std::move(compiled), devices_for_files(n_files));
+        std::vector<int> plan_of(static_cast<size_t>(n_files), 0);
+        std::vector<std::vector<int32_t> > pairs(static_cast<size_t>(n_files));
+        schedule_single_end(n_files, set, paths, nthreads, [&](scg_plan* P, int32_t f) {
+            random_harvest(P, pairs[static_cast<size_t>(f)]);
+            totals_out[f] = narrow_total(P->total);
+            for (size_t p = 0; p < set.plans.size(); ++p) if (set.plans[p].get() == P) plan_of[static_cast<size_t>(f)] = static_cast<int>(p);
+        });
+        result_random_matrix(set, plan_of, pairs, sequences_out, k_out, length_out, col_ptr_out, rows_out, freq_out);
     });
 }
 

@@ -221,6 +221,11 @@ using namespace scgapi;
 struct RandomTally {
     DevBuf tags, counts, arena;     // capacity slots: uint64 tag, uint64 count, vlen key bytes (hashed tags only)
     DevBuf state;                   // ScgRandomTable::state: first unknown-base error, occupied slots, unresolved reads
+    // Files mode (scg_count_random_barcodes_files): one table for all the files of a device.  A slot keeps a row id, a
+    // file's (id, count) pairs are harvested behind its last batch, and a soft reset clears counts and state words only.
+    bool files = false;
+    DevBuf ids;                     // capacity slots: uint32 row id
+    DevBuf harvest, harvest_n;      // a file's pairs and their number (launch_random_harvest)
     uint64_t cap = 0;
     int32_t vstart = 0, vlen = 0, tag_bits = 61;
     // growth bound: occupancy `known_occ` held after `known_at` reads; every read counted since may have added a key
@@ -245,6 +250,7 @@ struct RandomTally {
     scg::ScgRandomTable view() const {
         scg::ScgRandomTable t;
         t.tags = tags.as<unsigned long long>(); t.counts = counts.as<unsigned long long>(); t.arena = arena.as<uint8_t>();
+        t.ids = files ? ids.as<uint32_t>() : nullptr;
         t.state = state.as<unsigned long long>(); t.mask = cap - 1;
         t.vstart = vstart; t.vlen = vlen; t.tag_bits = tag_bits; t.pad = 0;
         return t;
@@ -395,6 +401,17 @@ std::unique_ptr<scg_plan> compile_random(const char* constant, int strand, int m
 void random_to_device(scg_plan* P);
 void random_reset(scg_plan* P, hipStream_t stream);
 void read_random(scg_plan* P, hipStream_t stream, char** sequences_out, int32_t** freq_out, int64_t* k_out, int32_t* length_out);
+// Files mode.  The soft reset before every file and after every decline of a ladder (reset_plan); one file's (id, count)
+// pairs behind its last batch, after the checks of read_random; at the end of the call every key the table ever held,
+// sorted byte-wise at stride vlen + 1, with its id.
+void random_soft_reset(scg_plan* P);
+void random_harvest(scg_plan* P, std::vector<int32_t>& pairs);
+struct RandomKeys {
+    std::unique_ptr<char, void (*)(void*)> bytes;      // malloc'd: K rows of vlen characters and a NUL, and one byte more
+    std::vector<unsigned long long> vals;              // K counts, or K ids
+    RandomKeys() : bytes(nullptr, std::free) {}
+};
+RandomKeys random_keys_with_ids(scg_plan* P);
 void launch_batch(scg_plan* P, const ScgReads& R, int64_t n, hipStream_t stream);
 void launch_batch_paired(scg_plan* P, const ScgReads& R1, const ScgReads& R2, int64_t n, hipStream_t stream);
 
@@ -524,6 +541,10 @@ std::vector<int> devices_for_files(int32_t n_files);
 void schedule_single_end(int32_t n_files, const PlanSet& set, const char* const* paths, int nthreads, const std::function<void(scg_plan*, int32_t)>& read_file);
 void schedule_paired(int32_t n_files, const PlanSet& set, const char* const* paths1, const char* const* paths2, int nthreads,
                      const std::function<void(scg_plan*, int32_t)>& read_file);
+// countRandomBarcodes over many files: per file the plan that counted it and its harvested (id, count) pairs -> the sorted
+// union of the keys some file counted and the files' columns in compressed-column form (scg_count_random_barcodes_files).
+void result_random_matrix(const PlanSet& set, const std::vector<int>& plan_of, const std::vector<std::vector<int32_t> >& pairs,
+                          char** sequences_out, int64_t* k_out, int32_t* length_out, int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out);
 void combo_compact(const int32_t* cells, int32_t n0, int32_t n1, int32_t** indices_out, int32_t** freq_out, int64_t* k_out);
 void combos_from_sparse(const std::unordered_map<uint64_t, int64_t>& m, int32_t** indices_out, int32_t** freq_out, int64_t* k_out);
 void diagnostics_from_counters(const scg_plan* P, const std::vector<int32_t>& all, int32_t* counts_out, int32_t** idx_out, int32_t** freq_out, int64_t* k_out,

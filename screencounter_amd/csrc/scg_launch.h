@@ -35,11 +35,14 @@ hipError_t launch_sort_rle(const uint64_t* d_keys, uint64_t* d_sorted, size_t n,
 // packed key of pure upper-case ACGT of at most 31 bases; bit 63 set = a hashed key, bits 61-62 the round, the hash of
 // the bytes below (kept to tag_bits bits).  state[0]: the first unknown-base error, (read ordinal << 8) | byte, ~0 if
 // none; state[1]: occupied slots; state[2]: reads whose key collided in every round.
+// Files mode (scg_count_random_barcodes_files; `ids` non-null): slot s also carries ids[s], the value of state[1] when
+// the slot was claimed -- a row number that stays with the key through every rehash and soft reset.
 #define SCG_RANDOM_ROUNDS 4
 struct ScgRandomTable {
     unsigned long long* tags;
     unsigned long long* counts;
     uint8_t* arena;
+    uint32_t* ids;             // null: plans of scg_plan_random keep no ids
     unsigned long long* state;
     uint64_t mask;
     int32_t vstart, vlen;      // the first forward variable region (the key on both strands)
@@ -55,12 +58,18 @@ hipError_t launch_random_insert(const ScgRandomTable& T, const ScgReads& R, int6
 // list_a, list_b: n entries each; lens: SCG_RANDOM_ROUNDS int32, zero on entry.
 hipError_t launch_random_verify_rounds(const ScgRandomTable& T, const ScgReads& R, int64_t n, const int32_t* hits, int32_t* slots,
                                        int32_t* list_a, int32_t* list_b, int32_t* lens, hipStream_t stream);
-// Moves every entry of `from` into `to` (empty, larger); tags are capacity-independent and distinct.
+// Moves every entry of `from` into `to` (empty, larger), ids included; tags are capacity-independent and distinct.
 hipError_t launch_random_rehash(const ScgRandomTable& from, const ScgRandomTable& to, hipStream_t stream);
+// Files mode, behind a file's last batch: every slot with a count appends (id, count) to `list` (pairs of int32, room for
+// list_cap of them) and its count is cleared; tag, key and id stay.  n_out[0]: pairs appended; n_out[1]: non-zero when a
+// count exceeds INT32_MAX or the list is too short (both zero on entry).  Nothing else may touch the table meanwhile.
+hipError_t launch_random_harvest(const ScgRandomTable& T, int32_t* list, uint32_t list_cap, unsigned int* n_out, hipStream_t stream);
 // Read-out: occupied slots with a count -> packed (tag, count) and hashed (slot, count) lists; n_out[0] / n_out[1]
-// their lengths (zero on entry); each list has room for every occupied slot.
+// their lengths (zero on entry); each list has room for every occupied slot.  with_ids: EVERY occupied slot, and its id
+// in the place of its count (the keys of a files-mode table, whose counts the harvests have taken).
 hipError_t launch_random_compact(const ScgRandomTable& T, unsigned long long* packed_tags, unsigned long long* packed_counts,
-                                 int32_t* hashed_slots, unsigned long long* hashed_counts, unsigned long long* n_out, hipStream_t stream);
+                                 int32_t* hashed_slots, unsigned long long* hashed_counts, unsigned long long* n_out, bool with_ids,
+                                 hipStream_t stream);
 size_t random_sort_scratch_bytes(size_t n);
 // Packed tags sorted with their counts on bits [0, end_bit): numeric order of packed tags is byte-wise order of the keys.
 hipError_t launch_random_sort(const unsigned long long* keys_in, unsigned long long* keys_out, const unsigned long long* vals_in,

@@ -482,10 +482,12 @@ const uint64_t RANDOM_MAX_SLOTS = uint64_t(1) << 30;     // slot indices travel 
 
 void swap_buf(DevBuf& a, DevBuf& b) { std::swap(a.p, b.p); std::swap(a.bytes, b.bytes); }
 
-void alloc_table(DevBuf& tags, DevBuf& counts, DevBuf& arena, uint64_t cap, int vlen) {
+// (ids: files mode only)
+void alloc_table(DevBuf& tags, DevBuf& counts, DevBuf& arena, DevBuf* ids, uint64_t cap, int vlen) {
     tags.alloc(cap * sizeof(unsigned long long));
     counts.alloc(cap * sizeof(unsigned long long));
     arena.alloc(cap * static_cast<uint64_t>(vlen));
+    if (ids) ids->alloc(cap * sizeof(uint32_t));
 }
 
 // Every call on the plan waits for the previous one, on whichever stream that ran.
@@ -523,9 +525,9 @@ void random_reserve(scg_plan* P, int64_t n, hipStream_t stream) {
         cap *= 2;
     }
     if (cap == T.cap) return;
-    DevBuf tags, counts, arena;
+    DevBuf tags, counts, arena, ids;
     try {
-        alloc_table(tags, counts, arena, cap, T.vlen);
+        alloc_table(tags, counts, arena, T.files ? &ids : nullptr, cap, T.vlen);
     } catch (const Error& e) {
         throw Error(SCG_ERR_DEVICE, "random barcode tally: cannot grow the table from " + std::to_string(T.cap) + " to " + std::to_string(cap) +
                     " slots (" + e.what() + "); no key was dropped, the counts so far stay readable");
@@ -535,9 +537,10 @@ void random_reserve(scg_plan* P, int64_t n, hipStream_t stream) {
     const scg::ScgRandomTable from = T.view();
     scg::ScgRandomTable to = from;
     to.tags = tags.as<unsigned long long>(); to.counts = counts.as<unsigned long long>(); to.arena = arena.as<uint8_t>(); to.mask = cap - 1;
+    if (T.files) to.ids = ids.as<uint32_t>();
     HIP_CHECK(scg::launch_random_rehash(from, to, stream));
     HIP_CHECK(hipStreamSynchronize(stream));          // before the old table is released
-    swap_buf(T.tags, tags); swap_buf(T.counts, counts); swap_buf(T.arena, arena);
+    swap_buf(T.tags, tags); swap_buf(T.counts, counts); swap_buf(T.arena, arena); swap_buf(T.ids, ids);
     T.cap = cap;
 }
 
@@ -578,7 +581,7 @@ void random_to_device(scg_plan* P) {
     RandomTally& T = *P->rnd;
     DeviceGuard g(P->device);
     T.cap = RANDOM_INITIAL_SLOTS;
-    alloc_table(T.tags, T.counts, T.arena, T.cap, T.vlen);
+    alloc_table(T.tags, T.counts, T.arena, T.files ? &T.ids : nullptr, T.cap, T.vlen);
     T.state.alloc(4 * sizeof(unsigned long long));
     T.snap.ensure(sizeof(unsigned long long));
     HIP_CHECK(hipEventCreateWithFlags(&T.snap_event, hipEventDisableTiming));
@@ -603,15 +606,11 @@ void random_reset(scg_plan* P, hipStream_t stream) {
     T.snap_pending = false;       // (a copy still in flight lands before any later one: the plan's calls are ordered)
 }
 
-// Read-out: occupied slots -> packed keys sorted on the device and decoded there, hashed keys' bytes sorted here; the two
-// sorted lists merged byte-wise (all keys have the same length).  Synchronises `stream`.
-void read_random(scg_plan* P, hipStream_t stream, char** sequences_out, int32_t** freq_out, int64_t* k_out, int32_t* length_out) {
-    RandomTally& T = *P->rnd;
-    DeviceGuard g(P->device);
-    random_order(T, stream);
-    unsigned long long st[4] = {0, 0, 0, 0};
-    HIP_CHECK(hipMemcpyAsync(st, T.state.p, sizeof(st), hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
+namespace {
+
+// What a read-out checks before it hands anything out, in this order: the reference's unknown-base error, reads longer
+// than their batch's declared maximum, reads whose key collided in every round.
+void check_random_state(scg_plan* P, const unsigned long long* st) {
     if (st[0] != ~0ull) {                              // kaori/utils.hpp:117, first offending read in counting order
         throw Error(SCG_ERR_INVALID, std::string("cannot complement unknown base '") + static_cast<char>(st[0] & 0xFF) + "'");
     }
@@ -620,14 +619,19 @@ void read_random(scg_plan* P, hipStream_t stream, char** sequences_out, int32_t*
         throw Error(SCG_ERR_UNSUPPORTED, "random barcode tally: the keys of " + std::to_string(st[2]) + " reads collided with other keys in all " +
                     std::to_string(SCG_RANDOM_ROUNDS) + " hash rounds; counts are incomplete");
     }
-    const uint64_t occ = st[1];
+}
+
+// Occupied slots (`occ` of them at most) -> packed keys sorted on the device and decoded there, hashed keys' bytes sorted
+// here; the two sorted lists merged byte-wise (all keys have the same length).  Each key comes with its count, and only
+// keys that have one; or, with_ids, every key with its id.  Synchronises `stream`.
+RandomKeys random_sorted_keys(RandomTally& T, hipStream_t stream, uint64_t occ, bool with_ids) {
     const int vlen = T.vlen;
     const size_t m = static_cast<size_t>(std::max<uint64_t>(occ, 1));
     DevBuf ptags, pcounts, hslots, hcounts, nout;
     ptags.alloc(m * 8); pcounts.alloc(m * 8); hslots.alloc(m * 4); hcounts.alloc(m * 8); nout.alloc(2 * 8);
     HIP_CHECK(hipMemsetAsync(nout.p, 0, 2 * 8, stream));
     HIP_CHECK(scg::launch_random_compact(T.view(), ptags.as<unsigned long long>(), pcounts.as<unsigned long long>(), hslots.as<int32_t>(),
-                                         hcounts.as<unsigned long long>(), nout.as<unsigned long long>(), stream));
+                                         hcounts.as<unsigned long long>(), nout.as<unsigned long long>(), with_ids, stream));
     unsigned long long nn[2] = {0, 0};
     HIP_CHECK(hipMemcpyAsync(nn, nout.p, sizeof(nn), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -662,31 +666,112 @@ void read_random(scg_plan* P, hipStream_t stream, char** sequences_out, int32_t*
             return std::memcmp(hb + a * vlen, hb + b * vlen, static_cast<size_t>(vlen)) < 0;
         });
     }
-    random_done(T, stream);
-    auto narrow = [](unsigned long long c) {
-        if (c > static_cast<unsigned long long>(INT32_MAX)) {
-            throw Error(SCG_ERR_INVALID, "frequency of a random barcode (" + std::to_string(c) + ") exceeds the 32-bit range of the count vectors");
-        }
-        return static_cast<int32_t>(c);
-    };
     const size_t K = np + nh;
-    OutPair<char, int32_t> out(K * stride + 1, K + 1);
-    char* so = out.a;
+    RandomKeys out;
+    out.bytes.reset(static_cast<char*>(std::malloc(K * stride + 1)));
+    if (!out.bytes) throw std::bad_alloc();
+    out.vals.resize(K);
+    char* so = out.bytes.get();
     size_t a = 0, b = 0;
     for (size_t k = 0; k < K; ++k) {
         const bool take_packed = b == nh ||
             (a < np && std::memcmp(pbytes.data() + a * stride, hbytes.data() + horder[b] * vlen, static_cast<size_t>(vlen)) < 0);
         if (take_packed) {
             std::memcpy(so + k * stride, pbytes.data() + a * stride, stride);
-            out.b[k] = narrow(pc[a++]);
+            out.vals[k] = pc[a++];
         } else {
             std::memcpy(so + k * stride, hbytes.data() + horder[b] * vlen, static_cast<size_t>(vlen));
             so[k * stride + vlen] = 0;
-            out.b[k] = narrow(hc[horder[b++]]);
+            out.vals[k] = hc[horder[b++]];
         }
     }
-    out.release(sequences_out, freq_out);
-    *k_out = static_cast<int64_t>(K); *length_out = vlen;
+    return out;
+}
+
+} // namespace
+
+// Read-out of a plan: the keys with a count, in the file entry's form.  Synchronises `stream`.
+void read_random(scg_plan* P, hipStream_t stream, char** sequences_out, int32_t** freq_out, int64_t* k_out, int32_t* length_out) {
+    RandomTally& T = *P->rnd;
+    DeviceGuard g(P->device);
+    random_order(T, stream);
+    unsigned long long st[4] = {0, 0, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(st, T.state.p, sizeof(st), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    check_random_state(P, st);
+    RandomKeys keys = random_sorted_keys(T, stream, st[1], false);
+    random_done(T, stream);
+    const size_t K = keys.vals.size();
+    std::unique_ptr<int32_t, void (*)(void*)> freq(static_cast<int32_t*>(std::malloc(sizeof(int32_t) * (K + 1))), std::free);
+    if (!freq) throw std::bad_alloc();
+    for (size_t k = 0; k < K; ++k) {
+        const unsigned long long c = keys.vals[k];
+        if (c > static_cast<unsigned long long>(INT32_MAX)) {
+            throw Error(SCG_ERR_INVALID, "frequency of a random barcode (" + std::to_string(c) + ") exceeds the 32-bit range of the count vectors");
+        }
+        freq.get()[k] = static_cast<int32_t>(c);
+    }
+    *sequences_out = keys.bytes.release(); *freq_out = freq.release();
+    *k_out = static_cast<int64_t>(K); *length_out = T.vlen;
+}
+
+// ---- files mode: one table for all the files a device takes (scg_count_random_barcodes_files) ----
+// These run between files, when the pipelines of the last one are gone: on the null stream, behind the plan's last call.
+
+// Counts, the error word and the unresolved reads go (the oversize-read flag and the total: reset_plan, the caller);
+// tags, keys, ids, occupancy and capacity stay.  A key first seen in a pass that was abandoned keeps its slot with a
+// count of zero, which no harvest lists.
+void random_soft_reset(scg_plan* P) {
+    RandomTally& T = *P->rnd;
+    DeviceGuard g(P->device);
+    unsigned long long* st = T.state.as<unsigned long long>();
+    random_order(T, nullptr);
+    HIP_CHECK(hipMemsetAsync(T.counts.p, 0, T.counts.bytes, nullptr));
+    HIP_CHECK(hipMemsetAsync(st, 0xFF, sizeof(unsigned long long), nullptr));
+    HIP_CHECK(hipMemsetAsync(st + 2, 0, 2 * sizeof(unsigned long long), nullptr));
+    HIP_CHECK(hipMemcpyAsync(T.snap.p, st + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, nullptr));
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    random_done(T, nullptr);
+    T.known_occ = static_cast<int64_t>(*T.snap.as<unsigned long long>());      // the growth bound starts over from the keys kept
+    T.known_at = 0;
+    T.snap_pending = false;
+    if (T.scratch.size() > 8) T.scratch.clear();       // (the host readers bring two new streams per file)
+}
+
+void random_harvest(scg_plan* P, std::vector<int32_t>& pairs) {
+    RandomTally& T = *P->rnd;
+    DeviceGuard g(P->device);
+    random_order(T, nullptr);
+    unsigned long long st[4] = {0, 0, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(st, T.state.p, sizeof(st), hipMemcpyDeviceToHost, nullptr));
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    check_random_state(P, st);
+    if (st[1] > static_cast<unsigned long long>(INT32_MAX)) throw Error(SCG_ERR_DEVICE, "internal: random barcode tally: occupancy out of range");
+    const uint32_t cap = static_cast<uint32_t>(st[1]);
+    T.harvest.ensure(static_cast<size_t>(std::max<uint32_t>(cap, 1)) * 2 * sizeof(int32_t));
+    T.harvest_n.ensure(2 * sizeof(unsigned int));
+    HIP_CHECK(hipMemsetAsync(T.harvest_n.p, 0, 2 * sizeof(unsigned int), nullptr));
+    HIP_CHECK(scg::launch_random_harvest(T.view(), T.harvest.as<int32_t>(), cap, T.harvest_n.as<unsigned int>(), nullptr));
+    unsigned int n[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(n, T.harvest_n.p, sizeof(n), hipMemcpyDeviceToHost, nullptr));
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    random_done(T, nullptr);
+    if (n[1] & 2u) throw Error(SCG_ERR_DEVICE, "internal: random barcode tally: more counted slots than occupied ones");
+    if (n[1]) throw Error(SCG_ERR_INVALID, "frequency of a random barcode exceeds the 32-bit range of the count vectors");
+    pairs.resize(static_cast<size_t>(n[0]) * 2);
+    if (n[0]) HIP_CHECK(hipMemcpy(pairs.data(), T.harvest.p, pairs.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+}
+
+RandomKeys random_keys_with_ids(scg_plan* P) {
+    RandomTally& T = *P->rnd;
+    DeviceGuard g(P->device);
+    random_order(T, nullptr);
+    unsigned long long occ = 0;
+    HIP_CHECK(hipMemcpyAsync(&occ, T.state.as<unsigned long long>() + 1, sizeof(occ), hipMemcpyDeviceToHost, nullptr));
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    RandomKeys keys = random_sorted_keys(T, nullptr, occ, true);
+    random_done(T, nullptr);
+    return keys;
 }
 
 // One batch of a single-end plan.  Combinations beyond the dense limit travel as a key stream (sparse mode); otherwise

@@ -11,7 +11,11 @@
 //            hash seed differs.  The rounds read their list length on the device and exit at once when it is 0.
 // Between workgroups of one launch only atomics pass information (the CAS result, the adds): no plain-stored byte is
 // handed off inside a launch, so neither the per-CU L1 nor the per-XCD L2s can serve a stale copy; every plain-stored
-// byte (arena, lists, slots) is read in a later launch on the same stream.
+// byte (arena, ids, lists, slots) is read in a later launch on the same stream.
+//
+// Files mode (scg_count_random_barcodes_files) keeps one table for all the files a device takes: the claimer of a slot
+// also stores a row id there (the occupancy counter's value), the harvest kernel takes a file's (id, count) pairs out and
+// clears the counts, and the keys leave the device once, at the end of the call, with their ids.
 #include <cstring>
 
 #include <hip/hip_runtime.h>
@@ -23,6 +27,7 @@ namespace scg {
 namespace {
 
 constexpr int RB = 256;                 // reads per workgroup
+constexpr int WAVE = 64;                // lanes of a gfx950 wavefront (RB is a multiple)
 constexpr int LDS_SLOTS = 2 * RB;       // LDS aggregation table: at most RB distinct tags, load <= 1/2
 constexpr int ROUND_GRID = 256;         // workgroups of the list rounds (grid-stride over a length known on the device)
 constexpr unsigned long long HASHED = 1ull << 63;
@@ -121,7 +126,10 @@ __device__ __forceinline__ int64_t table_insert(const ScgRandomTable& T, unsigne
         if (old == 0 || old == tag) {
             claimed = old == 0;
             atomicAdd(&T.counts[s], cnt);
-            if (claimed) atomicAdd(&T.state[1], 1ull);
+            if (claimed) {
+                const unsigned long long id = atomicAdd(&T.state[1], 1ull);
+                if (T.ids) T.ids[s] = (uint32_t)id;              // (like the arena bytes: read by later launches only)
+            }
             return (int64_t)s;
         }
         s = (s + 1) & T.mask;
@@ -246,6 +254,7 @@ __global__ __launch_bounds__(RB) void random_rehash_kernel(ScgRandomTable F, Scg
             t = (t + 1) & T.mask;
         }
         T.counts[t] = F.counts[s];
+        if (F.ids) T.ids[t] = F.ids[s];
         if (tag & HASHED) {
             const uint8_t* a = F.arena + s * (uint64_t)F.vlen;
             uint8_t* b = T.arena + t * (uint64_t)T.vlen;
@@ -256,17 +265,49 @@ __global__ __launch_bounds__(RB) void random_rehash_kernel(ScgRandomTable F, Scg
 
 __global__ __launch_bounds__(RB) void random_compact_kernel(ScgRandomTable T, unsigned long long* __restrict__ packed_tags,
                                                             unsigned long long* __restrict__ packed_counts, int32_t* __restrict__ hashed_slots,
-                                                            unsigned long long* __restrict__ hashed_counts, unsigned long long* __restrict__ n_out) {
+                                                            unsigned long long* __restrict__ hashed_counts, unsigned long long* __restrict__ n_out,
+                                                            bool with_ids) {
     const uint64_t cap = T.mask + 1;
     for (uint64_t s = (uint64_t)blockIdx.x * RB + threadIdx.x; s < cap; s += (uint64_t)gridDim.x * RB) {
-        const unsigned long long tag = T.tags[s], c = T.counts[s];
-        if (!tag || !c) continue;
+        const unsigned long long tag = T.tags[s];
+        if (!tag) continue;
+        const unsigned long long c = with_ids ? (unsigned long long)T.ids[s] : T.counts[s];
+        if (!with_ids && !c) continue;
         if (tag & HASHED) {
             const unsigned long long k = atomicAdd(&n_out[1], 1ull);
             hashed_slots[k] = (int32_t)s; hashed_counts[k] = c;
         } else {
             const unsigned long long k = atomicAdd(&n_out[0], 1ull);
             packed_tags[k] = tag; packed_counts[k] = c;
+        }
+    }
+}
+
+// One pass over the slots, a wavefront on 64 neighbouring ones at a time (the trip count is the same for a whole
+// workgroup, so every ballot sees all 64 lanes).  The lanes whose slot has a count take consecutive places in the list
+// from one atomic add of their first lane.
+__global__ __launch_bounds__(RB) void random_harvest_kernel(ScgRandomTable T, int32_t* __restrict__ list, uint32_t list_cap,
+                                                            unsigned int* __restrict__ n_out) {
+    const uint64_t cap = T.mask + 1;
+    const int lane = (int)(threadIdx.x & (WAVE - 1));
+    for (uint64_t base = (uint64_t)blockIdx.x * RB; base < cap; base += (uint64_t)gridDim.x * RB) {
+        const uint64_t s = base + threadIdx.x;
+        const unsigned long long c = s < cap ? T.counts[s] : 0ull;
+        const unsigned long long takers = __ballot(c != 0);
+        if (!takers) continue;
+        const int first_lane = __ffsll(takers) - 1;
+        unsigned int first = 0;
+        if (lane == first_lane) first = atomicAdd(&n_out[0], (unsigned int)__popcll(takers));
+        first = (unsigned int)__shfl((int)first, first_lane);
+        if (c != 0) {
+            const unsigned int k = first + (unsigned int)__popcll(takers & ((1ull << lane) - 1ull));
+            if (c > 0x7FFFFFFFull || k >= list_cap) {
+                atomicOr(&n_out[1], c > 0x7FFFFFFFull ? 1u : 2u);
+            } else {
+                list[2 * (size_t)k] = (int32_t)T.ids[s];
+                list[2 * (size_t)k + 1] = (int32_t)c;
+            }
+            T.counts[s] = 0;
         }
     }
 }
@@ -319,9 +360,17 @@ hipError_t launch_random_rehash(const ScgRandomTable& from, const ScgRandomTable
 }
 
 hipError_t launch_random_compact(const ScgRandomTable& T, unsigned long long* packed_tags, unsigned long long* packed_counts,
-                                 int32_t* hashed_slots, unsigned long long* hashed_counts, unsigned long long* n_out, hipStream_t stream) {
+                                 int32_t* hashed_slots, unsigned long long* hashed_counts, unsigned long long* n_out, bool with_ids,
+                                 hipStream_t stream) {
+    if (with_ids && !T.ids) return hipErrorInvalidValue;
     hipLaunchKernelGGL(random_compact_kernel, dim3(table_grid(T.mask + 1)), dim3(RB), 0, stream, T, packed_tags, packed_counts,
-                       hashed_slots, hashed_counts, n_out);
+                       hashed_slots, hashed_counts, n_out, with_ids);
+    return hipGetLastError();
+}
+
+hipError_t launch_random_harvest(const ScgRandomTable& T, int32_t* list, uint32_t list_cap, unsigned int* n_out, hipStream_t stream) {
+    if (!T.ids) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(random_harvest_kernel, dim3(table_grid(T.mask + 1)), dim3(RB), 0, stream, T, list, list_cap, n_out);
     return hipGetLastError();
 }
 

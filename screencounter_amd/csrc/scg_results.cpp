@@ -14,6 +14,7 @@ void reset_plan(scg_plan* P) {
     drop_pending_pairs(P);                                  // (sparse mode: batches in flight are let finish and dropped)
     P->sparse_counts.clear();
     P->total = 0;
+    if (P->kind == scg_plan::RANDOM && P->rnd->files) random_soft_reset(P);    // (the table's keys and ids stay for the next file)
 }
 
 // The reference's totals and counters are 32-bit `int`s (SingleBarcodeSingleEnd.hpp:132-133) and R integers
@@ -117,6 +118,11 @@ std::unique_ptr<scg_plan> clone_compiled(const scg_plan& a) {
     b->first1 = a.first1; b->first2 = a.first2;
     b->n_counters = a.n_counters;
     b->sparse = a.sparse;
+    if (a.rnd) {                                            // (the tally's settings; its table is made by random_to_device)
+        b->rnd.reset(new RandomTally);
+        b->rnd->vstart = a.rnd->vstart; b->rnd->vlen = a.rnd->vlen; b->rnd->tag_bits = a.rnd->tag_bits;
+        b->rnd->files = a.rnd->files;
+    }
     return b;
 }
 
@@ -261,7 +267,10 @@ void diagnostics_from_counters(const scg_plan* P, const std::vector<int32_t>& al
 PlanSet::PlanSet(std::unique_ptr<scg_plan> compiled, const std::vector<int>& devices) {
     for (size_t i = 1; i < devices.size(); ++i) plans.push_back(clone_compiled(*compiled));
     plans.insert(plans.begin(), std::move(compiled));
-    for (size_t i = 0; i < plans.size(); ++i) plans[i]->to_device(devices[i]);
+    for (size_t i = 0; i < plans.size(); ++i) {
+        plans[i]->to_device(devices[i]);
+        if (plans[i]->kind == scg_plan::RANDOM) random_to_device(plans[i].get());
+    }
 }
 std::vector<scg_plan*> PlanSet::all() const {
     std::vector<scg_plan*> v;
@@ -334,6 +343,85 @@ void result_diagnostics(const std::vector<scg_plan*>& plans, int32_t* counts_out
     diagnostics_from_counters(P, all, counts_out, idx_out, freq_out, k_out, b1_out ? b1_out : &b1, b2_out ? b2_out : &b2,
                               P->sparse ? &sparse : nullptr);
     *total_out = total;
+}
+
+// The matrix of matrixOfRandomBarcodes (R/countRandomBarcodes.R:87-92).  Every plan's keys come sorted with their ids;
+// the lists -- one per device, as a rule -- are merged with memcmp, equal keys of several plans sharing a row, and a key
+// that no file counted (first seen in a pass that was abandoned) gets no row.
+void result_random_matrix(const PlanSet& set, const std::vector<int>& plan_of, const std::vector<std::vector<int32_t> >& pairs,
+                          char** sequences_out, int64_t* k_out, int32_t* length_out, int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out) {
+    const size_t n_plans = set.plans.size(), n_files = pairs.size();
+    const int vlen = set.first()->rnd->vlen;
+    const size_t stride = static_cast<size_t>(vlen) + 1;
+    std::vector<RandomKeys> keys(n_plans);
+    std::vector<std::vector<int64_t> > row_of_id(n_plans);    // id -> place in the plan's sorted list
+    std::vector<std::vector<char> > counted(n_plans);         // by place in the plan's sorted list
+    for (size_t p = 0; p < n_plans; ++p) {
+        keys[p] = random_keys_with_ids(set.plans[p].get());
+        const size_t n = keys[p].vals.size();
+        row_of_id[p].assign(n, -1);
+        counted[p].assign(n, 0);
+        for (size_t i = 0; i < n; ++i) {
+            if (keys[p].vals[i] >= n || row_of_id[p][keys[p].vals[i]] >= 0) throw Error(SCG_ERR_DEVICE, "internal: random barcode tally: row ids are not a permutation");
+            row_of_id[p][keys[p].vals[i]] = static_cast<int64_t>(i);
+        }
+    }
+    size_t nnz = 0;
+    for (size_t f = 0; f < n_files; ++f) {
+        const size_t p = static_cast<size_t>(plan_of[f]);
+        for (size_t j = 0; j < pairs[f].size(); j += 2) {
+            const int32_t id = pairs[f][j];
+            if (id < 0 || static_cast<size_t>(id) >= row_of_id[p].size()) throw Error(SCG_ERR_DEVICE, "internal: random barcode tally: row id out of range");
+            counted[p][static_cast<size_t>(row_of_id[p][id])] = 1;
+        }
+        nnz += pairs[f].size() / 2;
+    }
+    // the union: the smallest key under the plans' cursors takes the next row, in every plan that holds it
+    std::vector<size_t> at(n_plans, 0);
+    std::vector<std::vector<int64_t> > row_of_place(n_plans);  // place in the plan's sorted list -> row of the union (-1: no file counted it)
+    for (size_t p = 0; p < n_plans; ++p) row_of_place[p].assign(counted[p].size(), -1);
+    std::vector<const char*> union_keys;
+    for (;;) {
+        const char* least = nullptr;
+        for (size_t p = 0; p < n_plans; ++p) {
+            while (at[p] < counted[p].size() && !counted[p][at[p]]) ++at[p];
+            if (at[p] == counted[p].size()) continue;
+            const char* k = keys[p].bytes.get() + at[p] * stride;
+            if (!least || std::memcmp(k, least, static_cast<size_t>(vlen)) < 0) least = k;
+        }
+        if (!least) break;
+        for (size_t p = 0; p < n_plans; ++p) {
+            if (at[p] < counted[p].size() && std::memcmp(keys[p].bytes.get() + at[p] * stride, least, static_cast<size_t>(vlen)) == 0) {
+                row_of_place[p][at[p]++] = static_cast<int64_t>(union_keys.size());
+            }
+        }
+        union_keys.push_back(least);
+    }
+    const size_t K = union_keys.size();
+    if (K > static_cast<size_t>(INT32_MAX)) throw Error(SCG_ERR_INVALID, "number of distinct random barcodes exceeds the 32-bit range of the row indices");
+    OutPair<char, int64_t> head(K * stride + 1, n_files + 1);
+    OutPair<int32_t, int32_t> body(nnz + 1, nnz + 1);
+    for (size_t k = 0; k < K; ++k) {
+        std::memcpy(head.a + k * stride, union_keys[k], static_cast<size_t>(vlen));
+        head.a[k * stride + vlen] = 0;
+    }
+    std::vector<std::pair<int32_t, int32_t> > column;
+    size_t filled = 0;
+    for (size_t f = 0; f < n_files; ++f) {
+        const size_t p = static_cast<size_t>(plan_of[f]);
+        head.b[f] = static_cast<int64_t>(filled);
+        column.clear();
+        for (size_t j = 0; j < pairs[f].size(); j += 2) {
+            const int64_t place = row_of_id[p][pairs[f][j]];
+            column.push_back(std::make_pair(static_cast<int32_t>(row_of_place[p][place]), pairs[f][j + 1]));
+        }
+        std::sort(column.begin(), column.end());
+        for (const auto& e : column) { body.a[filled] = e.first; body.b[filled] = e.second; ++filled; }
+    }
+    head.b[n_files] = static_cast<int64_t>(filled);
+    head.release(sequences_out, col_ptr_out);
+    body.release(rows_out, freq_out);
+    *k_out = static_cast<int64_t>(K); *length_out = vlen;
 }
 
 void with_per_file_outputs(int32_t** idx_out, int32_t** freq_out, int64_t* k_out, int32_t n_files, const std::function<void()>& body) {

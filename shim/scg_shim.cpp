@@ -158,13 +158,13 @@ Rcpp::List match_barcodes(Rcpp::CharacterVector sequences, Rcpp::CharacterVector
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Many files in one native call: optional additions for the matrixOf* functions.  With these seven exported, e.g.
+// Many files in one native call: optional additions for the matrixOf* functions.  With these eight exported, e.g.
 // matrixOfSingleBarcodes (R/countSingleBarcodes.R:112-126) replaces its
 //     out <- bplapply(files, FUN=countSingleBarcodes, ..., BPPARAM=BPPARAM)
 // by one call whose result it unpacks into the same per-file list; libscg schedules the files over the GPUs itself
 // (one file at a time per device, library compiled once), so no BiocParallel worker processes are needed.  The same
-// goes for matrixOfDualBarcodes (with and without include.invalid), matrixOfDualBarcodesSingleEnd (likewise) and
-// matrixOfPairedComboBarcodes: INTEGRATION.md lists which wrapper reaches which export.
+// goes for matrixOfDualBarcodes (with and without include.invalid), matrixOfDualBarcodesSingleEnd (likewise),
+// matrixOfPairedComboBarcodes and matrixOfRandomBarcodes: INTEGRATION.md lists which wrapper reaches which export.
 // ---------------------------------------------------------------------------------------------------------------
 
 namespace {
@@ -330,4 +330,27 @@ Rcpp::List count_combo_barcodes_paired_files(Rcpp::CharacterVector paths1, std::
                                     Rcpp::IntegerVector::create(b1[i]), Rcpp::IntegerVector::create(b2[i]));
     }
     return out;
+}
+
+// matrixOfRandomBarcodes (R/countRandomBarcodes.R:84-104): List(sequences, counts matrix, totals) -- the rows are the sorted
+// union of the files' sequences, column f what count_random_barcodes() counts in file f, zero where it found none.
+//[[Rcpp::export(rng=false)]]
+Rcpp::List count_random_barcodes_files(Rcpp::CharacterVector paths, std::string constant, int strand, int mismatches, bool use_first,
+                                       int nthreads) {
+    auto f = borrow(paths);
+    char* seqs = nullptr; int64_t* col_ptr = nullptr; int32_t *rows = nullptr, *freq = nullptr; int64_t k = 0; int32_t len = 0;
+    Rcpp::IntegerVector totals(paths.size());
+    char err[1024];
+    check(scg_count_random_barcodes_files(f.data(), (int32_t)f.size(), constant.c_str(), strand, mismatches, use_first, nthreads,
+                                          &seqs, &k, &len, &col_ptr, &rows, &freq, totals.begin(), err, sizeof(err)), err);
+    // (the arrays are released below also when an allocation on the R side throws)
+    struct Release { void *a, *b, *c, *d; ~Release() { scg_free(a); scg_free(b); scg_free(c); scg_free(d); } } release{seqs, col_ptr, rows, freq};
+    Rcpp::CharacterVector sequences(k);
+    for (int64_t i = 0; i < k; ++i) sequences[i] = std::string(seqs + i * (len + 1), len);
+    Rcpp::IntegerMatrix counts((int)k, paths.size());               // zero-filled; column f = file f
+    for (R_xlen_t c = 0; c < paths.size(); ++c) {
+        int* column = counts.column_begin(c);
+        for (int64_t j = col_ptr[c]; j < col_ptr[c + 1]; ++j) column[rows[j]] = freq[j];
+    }
+    return Rcpp::List::create(sequences, counts, totals);
 }
