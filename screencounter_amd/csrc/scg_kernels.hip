@@ -38,6 +38,66 @@ constexpr int BLOCK = 256;
 #endif
 
 // ---------------------------------------------------------------------------------------------
+// Match policies of the handlers' "best" searches and the two ways a result leaves a kernel.  Each is shared by the
+// general and the staged function of its handler; the use_first exits stay in the loops.
+// ---------------------------------------------------------------------------------------------
+// SimpleSingleMatch::search_best (SimpleSingleMatch.hpp:265-289): the fewest mismatches win, a tie between two
+// different barcodes is no match.  Start from {max_mm + 1, -1, false}; `best` is the winner's mismatches when found.
+struct BestSingle {
+    int best, index;
+    bool found;
+    __device__ __forceinline__ void offer(int idx, int tot) {
+        if (tot == best) {
+            if (index != idx) { found = false; index = -1; }
+        } else if (tot < best) {
+            found = true; best = tot; index = idx;
+        }
+    }
+    __device__ __forceinline__ int result() const { return found ? index : -1; }
+};
+
+// CombinatorialBarcodesSingleEnd.hpp:225-241: the same over a combination.  Start from {max_mm + 1, {0, 0}, false}.
+struct BestCombo {
+    int best, id[SCG_COMBO_REGIONS];
+    bool found;
+    __device__ __forceinline__ void take(const int cand[SCG_COMBO_REGIONS]) { found = true; id[0] = cand[0]; id[1] = cand[1]; }
+    __device__ __forceinline__ void offer(const int cand[SCG_COMBO_REGIONS], int tot) {
+        if (tot > best) return;
+        if (tot == best) {
+            if (id[0] != cand[0] || id[1] != cand[1]) found = false;
+        } else {
+            found = true; best = tot; id[0] = cand[0]; id[1] = cand[1];
+        }
+    }
+};
+
+// DualBarcodesPairedEnd.hpp:333-341 within one orientation (offer) and :363-371 across the two (merge).  Start from
+// {-1, max_mm1 + max_mm2 + 1}.
+struct BestPair {
+    int chosen, best;
+    __device__ __forceinline__ void offer(int idx, int cur) {
+        if (cur < best) { chosen = idx; best = cur; }
+        else if (cur == best && chosen != idx) { chosen = -1; }
+    }
+    __device__ __forceinline__ void merge(const BestPair& swapped) {
+        if (chosen < 0 || best > swapped.best) { chosen = swapped.chosen; best = swapped.best; }
+        else if (best == swapped.best && chosen != swapped.chosen) { chosen = -1; }
+    }
+};
+
+// Read (or pair) i matched barcode idx, or none (-1): to the index stream (ScgCounters::unit_index) or straight to its counter.
+__device__ __forceinline__ void emit_index(const ScgCounters& counts, int64_t i, int idx) {
+    if (counts.unit_index) counts.unit_index[i] = idx;
+    else if (idx >= 0) count_one(counts, idx);
+}
+
+// Read i gave the combination (id0, id1) of pools of n0 x n1, or none: to the pair stream (sparse mode) or to its cell.
+__device__ __forceinline__ void emit_combo(const ScgCounters& cells, int64_t i, bool found, int id0, int id1, int n1) {
+    if (cells.unit_pair) cells.unit_pair[i] = found ? (((uint64_t)(uint32_t)id0 << 32) | (uint32_t)id1) : ~0ull;
+    else if (found) count_one(cells, (int64_t)id0 * n1 + id1);
+}
+
+// ---------------------------------------------------------------------------------------------
 // single
 // ---------------------------------------------------------------------------------------------
 // Key of the template's variable regions at window position p, concatenated in read order (one
@@ -69,7 +129,7 @@ __device__ __forceinline__ int single_read(const ScgSingleParams& P, const Read&
     const ScgTemplate* T = P.tmpl;
     const int len = T->len;
     const int max_mm = P.max_mm;
-    int found = 0, index = -1, best = max_mm + 1;
+    BestSingle hit{max_mm + 1, -1, false};
     for (int p = 0; p + len <= rd.n; ++p) {
         for (int s = 0; s < 2; ++s) {                 // forward before reverse at each position
             if (s == 0 ? !P.fwd : !P.rev) continue;
@@ -79,17 +139,11 @@ __device__ __forceinline__ int single_read(const ScgSingleParams& P, const Read&
             int idx, d;
             index_match<W>(P.index, q, max_mm - c, idx, d);
             if (idx < 0) continue;
-            int tot = c + d;
-            if (P.use_first) {
-                return idx;                           // SimpleSingleMatch.hpp:207-224 (tot <= max_mm by construction)
-            } else if (tot == best) {                 // :265-289
-                if (index != idx) { found = 0; index = -1; }
-            } else if (tot < best) {
-                found = 1; best = tot; index = idx;
-            }
+            if (P.use_first) return idx;              // SimpleSingleMatch.hpp:207-224 (c + d <= max_mm by construction)
+            hit.offer(idx, c + d);
         }
     }
-    return found ? index : -1;
+    return hit.result();
 }
 
 template<class W>
@@ -98,9 +152,7 @@ __global__ __launch_bounds__(BLOCK) void single_kernel(ScgSingleParams P, ScgRea
     int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n_reads) return;
     Read rd = get_read(R, i);
-    int idx = single_read<W>(P, rd);
-    if (counts.unit_index) counts.unit_index[i] = idx;       // index-stream output (ScgCounters::unit_index)
-    else if (idx >= 0) count_one(counts, idx);
+    emit_index(counts, i, single_read<W>(P, rd));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -162,32 +214,23 @@ __device__ __forceinline__ bool combo_candidate(const ScgComboParams& P, const R
     return true;
 }
 
-// Returns 1 and fills best_id when the read yields a combination.
 template<class W>
-__device__ __forceinline__ int combo_read(const ScgComboParams& P, const Read& rd, int best_id[SCG_COMBO_REGIONS]) {
+__device__ __forceinline__ BestCombo combo_read(const ScgComboParams& P, const Read& rd) {
     const ScgTemplate* T = P.tmpl;
     const int len = T->len;
-    int found = 0, best = P.max_mm + 1;
-    for (int p = 0; p + len <= rd.n && !(found && P.use_first); ++p) {
+    BestCombo hit{P.max_mm + 1, {0, 0}, false};
+    for (int p = 0; p + len <= rd.n && !(hit.found && P.use_first); ++p) {
         for (int s = 0; s < 2; ++s) {
             if (s == 0 ? !P.fwd : !P.rev) continue;
             int c = const_mismatches(T, s != 0, rd.p, p, P.max_mm);
             if (c > P.max_mm) continue;
             int cand[SCG_COMBO_REGIONS], tot;
             if (!combo_candidate<W>(P, rd, p, s != 0, c, cand, tot)) continue;
-            if (P.use_first) {                          // :197-217
-                found = 1; best_id[0] = cand[0]; best_id[1] = cand[1];
-                break;
-            } else if (tot <= best) {                   // :225-241
-                if (tot == best) {
-                    if (best_id[0] != cand[0] || best_id[1] != cand[1]) found = 0;
-                } else {
-                    found = 1; best = tot; best_id[0] = cand[0]; best_id[1] = cand[1];
-                }
-            }
+            if (P.use_first) { hit.take(cand); break; } // :197-217
+            hit.offer(cand, tot);
         }
     }
-    return found;
+    return hit;
 }
 
 template<class W>
@@ -197,23 +240,22 @@ __global__ __launch_bounds__(BLOCK) void combo_kernel(ScgComboParams P, ScgReads
     if (i >= n_reads) return;
     if (P.only_if_negative && P.only_if_negative[i] >= 0) return;      // second pass of the single-end dual diagnostics
     Read rd = get_read(R, i);
-    int best_id[SCG_COMBO_REGIONS] = {0, 0};
-    const bool found = combo_read<W>(P, rd, best_id) != 0;
-    if (cells.unit_pair) cells.unit_pair[i] = found ? (((uint64_t)(uint32_t)best_id[0] << 32) | (uint32_t)best_id[1]) : ~0ull;
-    else if (found) count_one(cells, (int64_t)best_id[0] * P.n_pool[1] + best_id[1]);
+    const BestCombo hit = combo_read<W>(P, rd);
+    emit_combo(cells, i, hit.found, hit.id[0], hit.id[1], P.n_pool[1]);
 }
 
 // ---------------------------------------------------------------------------------------------
 // dual (paired-end)
 // ---------------------------------------------------------------------------------------------
-// One orientation: template 1 on read a, template 2 on read b.
-// use_first: index of the first valid (hit1, hit2) combination or -1.
+// One orientation: template 1 on read a, template 2 on read b.  !BEST (use_first): the first valid (hit1, hit2)
+// combination, DualBarcodesPairedEnd.hpp:264-276.  BEST: (chosen, best mismatches) as :310-347.
 template<class W>
-__device__ __forceinline__ int dual_first(const ScgDualParams& P, const Read& a, const Read& b) {
+__device__ __forceinline__ BestPair dual_search(const ScgDualParams& P, const bool BEST, const Read& a, const Read& b) {
     const ScgTemplate* T1 = P.tmpl1;
     const ScgTemplate* T2 = P.tmpl2;
     int s1 = P.rev1 ? T1->rstart[0] : T1->fstart[0];
     int s2 = P.rev2 ? T2->rstart[0] : T2->fstart[0];
+    BestPair hit{-1, P.max_mm1 + P.max_mm2 + 1};
     for (int p1 = 0; p1 + T1->len <= a.n; ++p1) {
         int c1 = const_mismatches(T1, P.rev1 != 0, a.p, p1, P.max_mm1);
         if (c1 > P.max_mm1) continue;
@@ -224,38 +266,12 @@ __device__ __forceinline__ int dual_first(const ScgDualParams& P, const Read& a,
             QueryT<W> q2 = pack_region<W>(b.p + p2 + s2, P.index2.len, P.rev2 != 0);
             int idx, tot;
             pair_match<W>(P.index1, P.index2, P.pairs, q1, P.max_mm1 - c1, q2, P.max_mm2 - c2, idx, tot);
-            if (idx >= 0) return idx;                   // DualBarcodesPairedEnd.hpp:264-276
+            if (idx < 0) continue;
+            if (!BEST) { hit.chosen = idx; return hit; }
+            hit.offer(idx, tot + c1 + c2);
         }
     }
-    return -1;
-}
-
-// best: (chosen, best_mismatches) as DualBarcodesPairedEnd.hpp:310-347
-template<class W>
-__device__ __forceinline__ void dual_best(const ScgDualParams& P, const Read& a, const Read& b, int& chosen, int& best) {
-    const ScgTemplate* T1 = P.tmpl1;
-    const ScgTemplate* T2 = P.tmpl2;
-    int s1 = P.rev1 ? T1->rstart[0] : T1->fstart[0];
-    int s2 = P.rev2 ? T2->rstart[0] : T2->fstart[0];
-    chosen = -1;
-    best = P.max_mm1 + P.max_mm2 + 1;
-    for (int p1 = 0; p1 + T1->len <= a.n; ++p1) {
-        int c1 = const_mismatches(T1, P.rev1 != 0, a.p, p1, P.max_mm1);
-        if (c1 > P.max_mm1) continue;
-        QueryT<W> q1 = pack_region<W>(a.p + p1 + s1, P.index1.len, P.rev1 != 0);
-        for (int p2 = 0; p2 + T2->len <= b.n; ++p2) {
-            int c2 = const_mismatches(T2, P.rev2 != 0, b.p, p2, P.max_mm2);
-            if (c2 > P.max_mm2) continue;
-            QueryT<W> q2 = pack_region<W>(b.p + p2 + s2, P.index2.len, P.rev2 != 0);
-            int idx, tot;
-            pair_match<W>(P.index1, P.index2, P.pairs, q1, P.max_mm1 - c1, q2, P.max_mm2 - c2, idx, tot);
-            if (idx >= 0) {                             // :333-341
-                int cur = tot + c1 + c2;
-                if (cur < best) { chosen = idx; best = cur; }
-                else if (cur == best && chosen != idx) { chosen = -1; }
-            }
-        }
-    }
+    return hit;
 }
 
 // SimpleSingleMatch::search_first / search_best of one mate on one strand (byte-wise), with the
@@ -263,9 +279,7 @@ __device__ __forceinline__ void dual_best(const ScgDualParams& P, const Read& a,
 template<class W>
 __device__ __forceinline__ bool mate_search(const ScgTemplate* T, const ScgIndex& X, bool reverse, int max_mm, bool use_first,
                                             bool keep_first, const Read& rd, int& index, int& mism) {
-    bool found = false;
-    index = -1; mism = 0;
-    int best = max_mm + 1;
+    BestSingle hit{max_mm + 1, -1, false};
     const int start = reverse ? T->rstart[0] : T->fstart[0];
     for (int p = 0; p + T->len <= rd.n; ++p) {
         int c = const_mismatches(T, reverse, rd.p, p, max_mm);
@@ -274,15 +288,11 @@ __device__ __forceinline__ bool mate_search(const ScgTemplate* T, const ScgIndex
         int idx, d;
         index_match<W>(X, q, max_mm - c, idx, d, keep_first);
         if (idx < 0) continue;
-        int tot = c + d;
-        if (use_first) { index = idx; mism = tot; return true; }
-        if (tot == best) {
-            if (index != idx) { found = false; index = -1; }
-        } else if (tot < best) {
-            found = true; best = tot; index = idx; mism = tot;
-        }
+        if (use_first) { index = idx; mism = c + d; return true; }
+        hit.offer(idx, c + d);
     }
-    return found;
+    index = hit.index; mism = hit.best;              // (mism is looked at only when found)
+    return hit.found;
 }
 
 // CombinatorialBarcodesPairedEnd::process (handlers/CombinatorialBarcodesPairedEnd.hpp:167-242) on a
@@ -349,21 +359,13 @@ __device__ __forceinline__ void diagnose_pair(const ScgDualParams& P, const M& m
 
 template<class W>
 __device__ __forceinline__ int dual_pair(const ScgDualParams& P, const Read& a, const Read& b) {
-    int idx;
     if (P.use_first) {                                  // :356-360
-        idx = dual_first<W>(P, a, b);
-        if (idx < 0 && P.randomized) idx = dual_first<W>(P, b, a);
-    } else {                                            // :362-376
-        int best;
-        dual_best<W>(P, a, b, idx, best);
-        if (P.randomized) {
-            int idx2, best2;
-            dual_best<W>(P, b, a, idx2, best2);
-            if (idx < 0 || best > best2) { idx = idx2; best = best2; }
-            else if (best == best2 && idx != idx2) { idx = -1; }
-        }
+        const int idx = dual_search<W>(P, false, a, b).chosen;
+        return idx < 0 && P.randomized ? dual_search<W>(P, false, b, a).chosen : idx;
     }
-    return idx;
+    BestPair hit = dual_search<W>(P, true, a, b);       // :362-376
+    if (P.randomized) hit.merge(dual_search<W>(P, true, b, a));
+    return hit.chosen;
 }
 
 template<class W>
@@ -406,15 +408,12 @@ __device__ __forceinline__ int single_read_staged(const ScgSingleParams& P, cons
 #ifdef SCG_ABLATE
     if (ablate == 1) return (candF[0] ^ candR[NC - 1]) == 0x12345u ? 0 : -1;
 #endif
-    int found = 0, index = -1, best = max_mm + 1;
+    BestSingle hit{max_mm + 1, -1, false};
     const int last = last_position(sr.n, T.len);
     for (;;) {
-        int pf = first_bit<NC>(candF), pr = first_bit<NC>(candR);
-        bool rev = pr < pf;                           // forward first on ties
-        int p = rev ? pr : pf;
-        if (p > last) break;                          // no candidate left inside the read (an empty mask gives 1 << 30)
-        clear_bit<NC>(candF, rev ? -1 : p);
-        clear_bit<NC>(candR, rev ? p : -1);
+        int p;
+        bool rev;
+        if (!next_candidate<NC>(candF, candR, last, p, rev)) break;
         int c = window_mismatches<NW, NT>(tile, sr.bit + p, st, rev);
         if (c > max_mm) continue;
         QueryT<W> q;
@@ -427,16 +426,10 @@ __device__ __forceinline__ int single_read_staged(const ScgSingleParams& P, cons
         int idx, d;
         index_match<W>(P.index, q, max_mm - c, idx, d);
         if (idx < 0) continue;
-        int tot = c + d;
-        if (P.use_first) {
-            return idx;
-        } else if (tot == best) {
-            if (index != idx) { found = 0; index = -1; }
-        } else if (tot < best) {
-            found = 1; best = tot; index = idx;
-        }
+        if (P.use_first) return idx;
+        hit.offer(idx, c + d);
     }
-    return found ? index : -1;
+    return hit.result();
 }
 
 // NC < NW ("compact"): candidate positions fit 32*NC bits and the plan's seeds allow it (ScgScan::compact_ok).
@@ -446,22 +439,10 @@ __global__ __launch_bounds__(STAGE_BLOCK, SCG_SINGLE_WAVES) __attribute__((amdgp
     __shared__ Tile<NW> tile;
     __shared__ StrandTable<NT> strands;
     fill_strand_table<NT>(strands, P.scan);
-    const int64_t r0 = (int64_t)blockIdx.x * STAGE_BLOCK;
-    const int nr = (int)((n_reads - r0) < STAGE_BLOCK ? (n_reads - r0) : STAGE_BLOCK);
-    int64_t span0 = 0;
-    const bool staged = (P.scan.len <= 32 * NT) && stage_reads<NW>(R, n_reads, r0, nr, tile, span0);
-    __syncthreads();
-    if ((int)threadIdx.x >= nr) return;
-    Read rd = get_read(R, r0 + threadIdx.x);
-    if (!staged || rd.n > 32 * NW) {
-        // The host picks the tile shape from the batch's maximum read length; landing here means
-        // that bound was wrong.  Flag it (reported by scg_plan_read) instead of guessing.
-        *error_flag = 1;
-        return;
-    }
     StagedRead sr;
-    sr.bit = (int)((int64_t)(rd.p - R.seqs) - span0);
-    sr.n = rd.n;
+    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, sr);
+    if (lane == Lane::idle) return;
+    if (lane == Lane::unstaged) { *error_flag = 1; return; }
     int idx;
 #ifdef SCG_ABLATE      // measurement builds only (phase ablation, tools/ablate_build.sh); never in the product library
     if (R.ablate == 2) {
@@ -473,8 +454,7 @@ __global__ __launch_bounds__(STAGE_BLOCK, SCG_SINGLE_WAVES) __attribute__((amdgp
 #else
     idx = single_read_staged<NW, NT, NC, W>(P, tile, strands, sr);
 #endif
-    if (counts.unit_index) counts.unit_index[r0 + threadIdx.x] = idx;
-    else if (idx >= 0) count_one(counts, idx);
+    emit_index(counts, lane_read(), idx);
 }
 
 template<int NW, int NT, int NC>
@@ -483,39 +463,26 @@ __global__ __launch_bounds__(STAGE_BLOCK) __attribute__((amdgpu_num_sgpr(80))) v
     __shared__ Tile<NW> tile;
     __shared__ StrandTable<NT> strands;
     fill_strand_table<NT>(strands, P.scan);
-    const int64_t r0 = (int64_t)blockIdx.x * STAGE_BLOCK;
-    const int nr = (int)((n_reads - r0) < STAGE_BLOCK ? (n_reads - r0) : STAGE_BLOCK);
-    int64_t span0 = 0;
-    const bool staged = (P.scan.len <= 32 * NT) && stage_reads<NW>(R, n_reads, r0, nr, tile, span0);
-    __syncthreads();
-    if ((int)threadIdx.x >= nr) return;
-    Read rd = get_read(R, r0 + threadIdx.x);
-    if (!staged || rd.n > 32 * NW) {
-        *error_flag = 1;
-        return;
-    }
     StagedRead sr;
-    sr.bit = (int)((int64_t)(rd.p - R.seqs) - span0);
-    sr.n = rd.n;
+    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, sr);
+    if (lane == Lane::idle) return;
+    if (lane == Lane::unstaged) { *error_flag = 1; return; }
     uint32_t candF[NC], candR[NC];
     scan_read<NW, NC>(tile, sr, P.scan, P.fwd != 0, P.rev != 0, candF, candR);
     BestHit h{P.max_mm + 1, -1, false};
     int out = -1;
     const int last = last_position(sr.n, P.scan.len);
     for (;;) {
-        int pf = first_bit<NC>(candF), pr = first_bit<NC>(candR);
-        bool rev = pr < pf;                           // forward first on ties
-        int p = rev ? pr : pf;
-        if (p > last) break;
-        clear_bit<NC>(candF, rev ? -1 : p);
-        clear_bit<NC>(candR, rev ? p : -1);
+        int p;
+        bool rev;
+        if (!next_candidate<NC>(candF, candR, last, p, rev)) break;
         int c = window_mismatches<NW, NT>(tile, sr.bit + p, strands, rev);
         if (c > P.max_mm) continue;
         if (P.use_first) { out = (p << 1) | (rev ? 1 : 0); break; }
         h.offer(c, p, rev);
     }
     if (!P.use_first && !h.tied && h.best <= P.max_mm) out = h.code;
-    hits[r0 + threadIdx.x] = out;
+    hits[lane_read()] = out;
 }
 
 // SECOND: the masked DuplicateAction::FIRST pass of the single-end dual diagnostics -- a compile-time variant, so that
@@ -558,62 +525,37 @@ __global__ __launch_bounds__(STAGE_BLOCK, SCG_COMBO_WAVES) __attribute__((amdgpu
         const uint32_t* src = reinterpret_cast<const uint32_t*>(&P.index[0]);
         reinterpret_cast<uint32_t*>(&pools[0])[threadIdx.x] = src[threadIdx.x];
     }
-    const int64_t r0 = (int64_t)blockIdx.x * STAGE_BLOCK;
-    const int nr = (int)((n_reads - r0) < STAGE_BLOCK ? (n_reads - r0) : STAGE_BLOCK);
-    int64_t span0 = 0;
-    const bool staged = (P.scan.len <= 32 * NT) && stage_reads<NW>(R, n_reads, r0, nr, tile, span0);
-    __syncthreads();
-    if ((int)threadIdx.x >= nr) return;
-    Read rd = get_read(R, r0 + threadIdx.x);
-    int found = 0, best = P.max_mm + 1;
-    int best_id[SCG_COMBO_REGIONS] = {0, 0};
-    if (!staged || rd.n > 32 * NW) {
-        *error_flag = 1;
-        return;
-    }
-    if (!(SECOND && P.only_if_negative[r0 + threadIdx.x] >= 0)) {   // (second pass: only reads the first pass left without a combination)
+    StagedRead sr;
+    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, sr);
+    if (lane == Lane::idle) return;
+    if (lane == Lane::unstaged) { *error_flag = 1; return; }
+    BestCombo hit{P.max_mm + 1, {0, 0}, false};
+    if (!(SECOND && P.only_if_negative[lane_read()] >= 0)) {   // (second pass: only reads the first pass left without a combination)
         const ScgScan& T = P.scan;
-        StagedRead sr;
-        sr.bit = (int)((int64_t)(rd.p - R.seqs) - span0);
-        sr.n = rd.n;
         uint32_t candF[NC], candR[NC];
         scan_read<NW, NC>(tile, sr, T, P.fwd != 0, P.rev != 0, candF, candR);
         const int last = last_position(sr.n, T.len);
         for (;;) {
-            int pf = first_bit<NC>(candF), pr = first_bit<NC>(candR);
-            bool rev = pr < pf;
-            int p = rev ? pr : pf;
-            if (p > last) break;
-            clear_bit<NC>(candF, rev ? -1 : p);
-            clear_bit<NC>(candR, rev ? p : -1);
+            int p;
+            bool rev;
+            if (!next_candidate<NC>(candF, candR, last, p, rev)) break;
             int c = window_mismatches<NW, NT>(tile, sr.bit + p, strands, rev);
             if (c > P.max_mm) continue;
             int cand[SCG_COMBO_REGIONS], tot;
             if (!combo_candidate_staged<NW, NT, SECOND, W>(P, pools, tile, strands, sr, p, rev, c, cand, tot)) continue;
-            if (P.use_first) {
-                found = 1; best_id[0] = cand[0]; best_id[1] = cand[1];
-                break;
-            } else if (tot <= best) {
-                if (tot == best) {
-                    if (best_id[0] != cand[0] || best_id[1] != cand[1]) found = 0;
-                } else {
-                    found = 1; best = tot; best_id[0] = cand[0]; best_id[1] = cand[1];
-                }
-            }
+            if (P.use_first) { hit.take(cand); break; }
+            hit.offer(cand, tot);
         }
     }
-    if (cells.unit_index) cells.unit_index[r0 + threadIdx.x] = found ? best_id[0] * P.n_pool[1] + best_id[1] : -1;     // tally mode
-    else if (cells.unit_pair) cells.unit_pair[r0 + threadIdx.x] = found ? (((uint64_t)(uint32_t)best_id[0] << 32) | (uint32_t)best_id[1]) : ~0ull;   // sparse mode
-    else if (found) count_one(cells, (int64_t)best_id[0] * P.n_pool[1] + best_id[1]);
+    if (cells.unit_index) cells.unit_index[lane_read()] = hit.found ? hit.id[0] * P.n_pool[1] + hit.id[1] : -1;     // tally mode
+    else emit_combo(cells, lane_read(), hit.found, hit.id[0], hit.id[1], P.n_pool[1]);
 }
 
 // Staged counterpart of mate_search.
 template<int NW, int NT, int NC, class W>
 __device__ __forceinline__ bool mate_search_staged(const Tile<NW>& tile, const StagedRead& sr, const ScgScan& T, const ScgIndex& X,
                                                    bool reverse, int max_mm, bool use_first, bool keep_first, int& index, int& mism) {
-    bool found = false;
-    index = -1; mism = 0;
-    int best = max_mm + 1;
+    BestSingle hit{max_mm + 1, -1, false};
     uint32_t cand[NC], unused[NC];
     // T carries the searched strand in its forward fields (searched_strand_first, scg_api.cpp); `reverse` only says how
     // the extracted region is to be read
@@ -621,48 +563,40 @@ __device__ __forceinline__ bool mate_search_staged(const Tile<NW>& tile, const S
     const int start = T.fstart[0];
     const int last = last_position(sr.n, T.len);
     for (;;) {
-        int p = first_bit<NC>(cand);
-        if (p > last) break;
-        clear_bit<NC>(cand, p);
+        int p;
+        if (!next_candidate<NC>(cand, last, p)) break;
         int c = window_mismatches<NW, NT>(tile, sr.bit + p, T, false);
         if (c > max_mm) continue;
         QueryT<W> q = region_query<NW, W>(tile, sr.bit + p + start, X.len, reverse);
         int idx, d;
         index_match<W>(X, q, max_mm - c, idx, d, keep_first);
         if (idx < 0) continue;
-        int tot = c + d;
-        if (use_first) { index = idx; mism = tot; return true; }
-        if (tot == best) {
-            if (index != idx) { found = false; index = -1; }
-        } else if (tot < best) {
-            found = true; best = tot; index = idx; mism = tot;
-        }
+        if (use_first) { index = idx; mism = c + d; return true; }
+        hit.offer(idx, c + d);
     }
-    return found;
+    index = hit.index; mism = hit.best;              // (mism is looked at only when found)
+    return hit.found;
 }
 
 // One orientation of a staged pair: template 1 on (ta, a), template 2 on (tb, b).
 template<int NW, int NT, int NC, class W>
-__device__ __forceinline__ void dual_orientation_staged(const ScgDualParams& P, const bool BEST,
-                                                        const Tile<NW>& ta, const StagedRead& a,
-                                                        const Tile<NW>& tb, const StagedRead& b,
-                                                        int& chosen, int& best) {
+__device__ __forceinline__ BestPair dual_orientation_staged(const ScgDualParams& P, const bool BEST,
+                                                            const Tile<NW>& ta, const StagedRead& a,
+                                                            const Tile<NW>& tb, const StagedRead& b) {
     const ScgScan& T1 = P.scan1;
     const ScgScan& T2 = P.scan2;
     const bool rev1 = P.rev1 != 0, rev2 = P.rev2 != 0;
     // both scans carry the searched strand in their forward fields (searched_strand_first, scg_api.cpp)
     const int s1 = T1.fstart[0];
     const int s2 = T2.fstart[0];
-    chosen = -1;
-    best = P.max_mm1 + P.max_mm2 + 1;
+    BestPair hit{-1, P.max_mm1 + P.max_mm2 + 1};
     uint32_t c1[NC], c2[NC], unused[NC];
     scan_read<NW, NC>(ta, a, T1, true, false, c1, unused);
     scan_read<NW, NC>(tb, b, T2, true, false, c2, unused);
     const int last1 = last_position(a.n, T1.len), last2 = last_position(b.n, T2.len);
     for (;;) {
-        int p1 = first_bit<NC>(c1);
-        if (p1 > last1) break;
-        clear_bit<NC>(c1, p1);
+        int p1;
+        if (!next_candidate<NC>(c1, last1, p1)) break;
         int m1 = window_mismatches<NW, NT>(ta, a.bit + p1, T1, false);
         if (m1 > P.max_mm1) continue;
         QueryT<W> q1 = region_query<NW, W>(ta, a.bit + p1 + s1, P.index1.len, rev1);
@@ -670,9 +604,8 @@ __device__ __forceinline__ void dual_orientation_staged(const ScgDualParams& P, 
 #pragma unroll
         for (int i = 0; i < NC; ++i) w2[i] = c2[i];
         for (;;) {
-            int p2 = first_bit<NC>(w2);
-            if (p2 > last2) break;
-            clear_bit<NC>(w2, p2);
+            int p2;
+            if (!next_candidate<NC>(w2, last2, p2)) break;
             int m2 = window_mismatches<NW, NT>(tb, b.bit + p2, T2, false);
             if (m2 > P.max_mm2) {
                 clear_bit<NC>(c2, p2);      // never a hit of mate 2: drop it for later outer iterations
@@ -681,14 +614,12 @@ __device__ __forceinline__ void dual_orientation_staged(const ScgDualParams& P, 
             QueryT<W> q2 = region_query<NW, W>(tb, b.bit + p2 + s2, P.index2.len, rev2);
             int idx, tot;
             pair_match<W>(P.index1, P.index2, P.pairs, q1, P.max_mm1 - m1, q2, P.max_mm2 - m2, idx, tot);
-            if (idx >= 0) {
-                if (!BEST) { chosen = idx; return; }
-                int cur = tot + m1 + m2;
-                if (cur < best) { chosen = idx; best = cur; }
-                else if (cur == best && chosen != idx) { chosen = -1; }
-            }
+            if (idx < 0) continue;
+            if (!BEST) { hit.chosen = idx; return hit; }
+            hit.offer(idx, tot + m1 + m2);
         }
     }
+    return hit;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -718,9 +649,8 @@ __device__ __forceinline__ void collect_hits(const Tile<NW>& tile, const StagedR
     h.count = 0; h.m = 0;
     h.q = QueryT<W>{};
     for (;;) {
-        int p = first_bit<NC>(cand);
-        if (p > last) break;
-        clear_bit<NC>(cand, p);
+        int p;
+        if (!next_candidate<NC>(cand, last, p)) break;
         int m = window_mismatches<NW, NT>(tile, sr.bit + p, T, false);
         if (m > max_mm) continue;
         if (h.count == 0) {
@@ -733,14 +663,13 @@ __device__ __forceinline__ void collect_hits(const Tile<NW>& tile, const StagedR
 
 // One orientation from what the passes kept: template 1's hit `x`, template 2's hit `y`.
 template<class W>
-__device__ __forceinline__ void dual_orientation_hits(const ScgDualParams& P, const bool BEST, const MateHits<W>& x, const MateHits<W>& y,
-                                                      int& chosen, int& best) {
-    chosen = -1;
-    best = P.max_mm1 + P.max_mm2 + 1;
-    if (x.count == 0 || y.count == 0) return;
+__device__ __forceinline__ BestPair dual_orientation_hits(const ScgDualParams& P, const MateHits<W>& x, const MateHits<W>& y) {
+    BestPair hit{-1, P.max_mm1 + P.max_mm2 + 1};
+    if (x.count == 0 || y.count == 0) return hit;
     int idx, tot;
     pair_match<W>(P.index1, P.index2, P.pairs, x.q, P.max_mm1 - x.m, y.q, P.max_mm2 - y.m, idx, tot);
-    if (idx >= 0) { chosen = idx; best = tot + x.m + y.m; }
+    if (idx >= 0) hit = BestPair{idx, tot + x.m + y.m};
+    return hit;
 }
 
 // The four mate searches of diagnose_pair, done while each mate was staged.
@@ -775,8 +704,7 @@ __device__ __forceinline__ void dual_pass(const int pass, const ScgDualParams& P
     if (!ok || !wanted) return;
     Read rd = get_read(R, r0 + threadIdx.x);
     if (rd.n > 32 * NW) { S.bad = true; return; }
-    StagedRead sr;
-    sr.bit = (int)((int64_t)(rd.p - R.seqs) - span); sr.n = rd.n;
+    const StagedRead sr = staged_read(R, rd, span);
     bool do1 = pass == 0 || RANDOMIZED, do2 = pass == 1 || RANDOMIZED;
     if (MATES_ONLY) {
         SearchedMates& sm = S.sm;
@@ -844,7 +772,6 @@ __global__ __launch_bounds__(STAGE_BLOCK) void dual_passes_kernel(ScgDualParams 
         diagnose_pair(P, S.sm, counts);
         return;
     }
-    int idx = -1;
     if (S.h1a.count > 1 || S.h2b.count > 1 || S.h1b.count > 1 || S.h2a.count > 1) {
         const int slot = atomicAdd(P.overflow, 1);
         P.overflow[1 + slot] = (int32_t)(r0 + threadIdx.x);          // (batches are below 2^31 pairs)
@@ -853,17 +780,12 @@ __global__ __launch_bounds__(STAGE_BLOCK) void dual_passes_kernel(ScgDualParams 
     }
     // One body for both orientations and both policies: DualBarcodesPairedEnd.hpp:353-381.
     const bool best_mode = !P.use_first;
-    int best;
-    dual_orientation_hits<W>(P, best_mode, S.h1a, S.h2b, idx, best);
-    if (RANDOMIZED && (best_mode || idx < 0)) {                      // :356-360, :363-371
-        int ci, cb;
-        dual_orientation_hits<W>(P, best_mode, S.h1b, S.h2a, ci, cb);
-        if (!best_mode) idx = ci;
-        else if (idx < 0 || best > cb) { idx = ci; best = cb; }
-        else if (best == cb && idx != ci) { idx = -1; }
+    BestPair hit = dual_orientation_hits<W>(P, S.h1a, S.h2b);
+    if (RANDOMIZED && (best_mode || hit.chosen < 0)) {               // :356-360, :363-371
+        const BestPair swapped = dual_orientation_hits<W>(P, S.h1b, S.h2a);
+        if (best_mode) hit.merge(swapped); else hit = swapped;
     }
-    if (counts.unit_index) counts.unit_index[r0 + threadIdx.x] = idx;       // index stream (ScgCounters::unit_index)
-    else if (idx >= 0) count_one(counts, idx);
+    emit_index(counts, r0 + threadIdx.x, hit.chosen);
 }
 
 // The pairs dual_passes_kernel listed, searched byte-wise like the general kernel does.  A fixed, small grid: the list is
@@ -874,9 +796,7 @@ __global__ __launch_bounds__(BLOCK) void dual_overflow_kernel(ScgDualParams P, S
     for (int k = blockIdx.x * BLOCK + threadIdx.x; k < n; k += gridDim.x * BLOCK) {
         const int64_t i = P.overflow[1 + k];
         Read a = get_read(R1, i), b = get_read(R2, i);
-        const int idx = dual_pair<W>(P, a, b);
-        if (counts.unit_index) counts.unit_index[i] = idx;
-        else if (idx >= 0) count_one(counts, idx);
+        emit_index(counts, i, dual_pair<W>(P, a, b));
     }
 }
 
@@ -900,32 +820,27 @@ __global__ __launch_bounds__(STAGE_BLOCK) void dual_staged_kernel(ScgDualParams 
         *error_flag = 1;
         return;
     }
-    StagedRead sa, sb;
-    sa.bit = (int)((int64_t)(a.p - R1.seqs) - span1); sa.n = a.n;
-    sb.bit = (int)((int64_t)(b.p - R2.seqs) - span2); sb.n = b.n;
+    const StagedRead sa = staged_read(R1, a, span1), sb = staged_read(R2, b, span2);
     // One body for both orientations (template 1 on mate 1 / on mate 2 when randomized) and
     // both policies: DualBarcodesPairedEnd.hpp:353-381.
     const bool best_mode = !P.use_first;
     const int norient = P.randomized ? 2 : 1;
-    int best = 0, idx = -1;
+    BestPair hit{-1, 0};
     for (int o = 0; o < norient; ++o) {
         const Tile<NW>* ta = o ? &tile2 : &tile1;
         const Tile<NW>* tb = o ? &tile1 : &tile2;
         const StagedRead ra = o ? sb : sa, rb = o ? sa : sb;
-        int ci, cb;
-        dual_orientation_staged<NW, NT, NC, W>(P, best_mode, *ta, ra, *tb, rb, ci, cb);
+        const BestPair cur = dual_orientation_staged<NW, NT, NC, W>(P, best_mode, *ta, ra, *tb, rb);
         if (!best_mode) {
-            idx = ci;
-            if (ci >= 0) break;                      // :356-360
+            hit = cur;
+            if (cur.chosen >= 0) break;              // :356-360
         } else if (o == 0) {
-            idx = ci; best = cb;
+            hit = cur;
         } else {                                     // :363-371
-            if (idx < 0 || best > cb) { idx = ci; best = cb; }
-            else if (best == cb && idx != ci) { idx = -1; }
+            hit.merge(cur);
         }
     }
-    if (counts.unit_index) counts.unit_index[r0 + threadIdx.x] = idx;       // index stream (ScgCounters::unit_index)
-    else if (idx >= 0) count_one(counts, idx);
+    emit_index(counts, r0 + threadIdx.x, hit.chosen);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1052,18 +967,40 @@ hipError_t dispatch_shape(int max_len, int tmpl_len, Args&&... args) {
     return wide ? Launch<10, 8>::go(args...) : Launch<5, 8>::go(args...);
 }
 
+// Compact variant of a staged kernel: all candidate positions (0 .. max_len - T) fit 3 words of a 5-word read.
+template<int NW>
+bool compact_fits(bool compact_ok, int max_len, int tmpl_len) { return NW == 5 && compact_ok && max_len - tmpl_len + 1 <= 96; }
+
+// A staged kernel's candidate words and key word as one type, handed to the callable of with_shape / with_key.
+template<int NC_, class W_> struct Shape {
+    static constexpr int NC = NC_;
+    using W = W_;
+};
+
+// f(Shape<NC, W>()) for the compact or the full candidate mask and 32- or 64-bit keys.
+template<int NW, class F>
+void with_shape(bool compact, bool wide, F&& f) {
+    constexpr int NCC = NW == 5 ? 3 : NW;
+    if (compact) { if (wide) f(Shape<NCC, uint64_t>()); else f(Shape<NCC, uint32_t>()); }
+    else { if (wide) f(Shape<NW, uint64_t>()); else f(Shape<NW, uint32_t>()); }
+}
+
+// f(Shape<0, W>()) for the key word of the general kernels and match_kernel: ScgIndex::wide 0 / 1 / 2 = keys of up to
+// 32 / 64 / 256 bases.
+template<class F>
+void with_key(int wide, F&& f) {
+    if (wide == 2) f(Shape<0, Big>());
+    else if (wide) f(Shape<0, uint64_t>());
+    else f(Shape<0, uint32_t>());
+}
+
 template<int NW, int NT> struct LaunchSingle {
     static hipError_t go(const ScgSingleParams& P, const ScgReads& R, int64_t n, const ScgCounters& counts, int32_t* flag, hipStream_t stream) {
-        // compact variant: all candidate positions (0 .. max_len - T) fit 3 words of a 5-word read
-        const bool compact = NW == 5 && P.scan.compact_ok && R.max_len - P.scan.len + 1 <= 96;
-        if (P.index.wide || P.scan.nreg != 1) {          // wide / concatenated keys
-            if (compact) hipLaunchKernelGGL((single_staged_kernel<NW, NT, (NW == 5 ? 3 : NW), uint64_t>), dim3(staged_grid(n)), dim3(STAGE_BLOCK), extra_lds(), stream, P, R, n, counts, flag);
-            else hipLaunchKernelGGL((single_staged_kernel<NW, NT, NW, uint64_t>), dim3(staged_grid(n)), dim3(STAGE_BLOCK), extra_lds(), stream, P, R, n, counts, flag);
-        } else if (compact) {
-            hipLaunchKernelGGL((single_staged_kernel<NW, NT, (NW == 5 ? 3 : NW), uint32_t>), dim3(staged_grid(n)), dim3(STAGE_BLOCK), extra_lds(), stream, P, R, n, counts, flag);
-        } else {
-            hipLaunchKernelGGL((single_staged_kernel<NW, NT, NW, uint32_t>), dim3(staged_grid(n)), dim3(STAGE_BLOCK), extra_lds(), stream, P, R, n, counts, flag);
-        }
+        const bool wide = P.index.wide || P.scan.nreg != 1;          // wide / concatenated keys
+        with_shape<NW>(compact_fits<NW>(P.scan.compact_ok, R.max_len, P.scan.len), wide, [&](auto s) {
+            using S = decltype(s);
+            hipLaunchKernelGGL((single_staged_kernel<NW, NT, S::NC, typename S::W>), dim3(staged_grid(n)), dim3(STAGE_BLOCK), extra_lds(), stream, P, R, n, counts, flag);
+        });
         return hipGetLastError();
     }
 };
@@ -1074,11 +1011,11 @@ template<int NW, int NT> struct LaunchCombo {
         else hipLaunchKernelGGL((combo_staged_kernel<NW, NT, NC, false, W>), dim3(staged_grid(n)), dim3(STAGE_BLOCK), extra_lds(), stream, P, R, n, cells, flag);
     }
     static hipError_t go(const ScgComboParams& P, const ScgReads& R, int64_t n, const ScgCounters& cells, int32_t* flag, hipStream_t stream) {
-        const bool compact = NW == 5 && P.scan.compact_ok && R.max_len - P.scan.len + 1 <= 96;
-        constexpr int NCC = NW == 5 ? 3 : NW;
         const bool wide = P.index[0].wide != 0;          // pools of 33..64 bases (both indexes are then built wide)
-        if (compact) { if (wide) run<NCC, uint64_t>(P, R, n, cells, flag, stream); else run<NCC, uint32_t>(P, R, n, cells, flag, stream); }
-        else { if (wide) run<NW, uint64_t>(P, R, n, cells, flag, stream); else run<NW, uint32_t>(P, R, n, cells, flag, stream); }
+        with_shape<NW>(compact_fits<NW>(P.scan.compact_ok, R.max_len, P.scan.len), wide, [&](auto s) {
+            using S = decltype(s);
+            run<S::NC, typename S::W>(P, R, n, cells, flag, stream);
+        });
         return hipGetLastError();
     }
 };
@@ -1119,15 +1056,16 @@ template<int NW, int NT> struct LaunchDual {
     static hipError_t go(const ScgDualParams& P, const ScgReads& R1, const ScgReads& R2, int64_t n, const ScgCounters& counts, int32_t* flag, hipStream_t stream) {
         const int max_len = R1.max_len > R2.max_len ? R1.max_len : R2.max_len;
         const int min_t = P.scan1.len < P.scan2.len ? P.scan1.len : P.scan2.len;
-        const bool compact = NW == 5 && P.scan1.compact_ok && P.scan2.compact_ok && max_len - min_t + 1 <= 96;
-        constexpr int NCC = NW == 5 ? 3 : NW;
+        const bool compact = compact_fits<NW>(P.scan1.compact_ok && P.scan2.compact_ok, max_len, min_t);
         if (P.diagnostics == 1) return hipErrorInvalidValue;   // the host runs include.invalid=TRUE as a plain pass followed by a masked pass of 2
         const bool wide = P.index1.wide != 0;            // barcodes of 33..64 bases on either mate (both indexes are then built wide)
         const int forced = two_tiles();
         const bool passes = P.overflow && (forced >= 0 ? forced == 0
                                            : expected_chance_hits(P.scan1, P.max_mm1, max_len) + expected_chance_hits(P.scan2, P.max_mm2, max_len) < 0.01);
-        if (compact) { if (wide) run<NCC, uint64_t>(P, R1, R2, n, counts, flag, stream, passes); else run<NCC, uint32_t>(P, R1, R2, n, counts, flag, stream, passes); }
-        else { if (wide) run<NW, uint64_t>(P, R1, R2, n, counts, flag, stream, passes); else run<NW, uint32_t>(P, R1, R2, n, counts, flag, stream, passes); }
+        with_shape<NW>(compact, wide, [&](auto s) {
+            using S = decltype(s);
+            run<S::NC, typename S::W>(P, R1, R2, n, counts, flag, stream, passes);
+        });
         return hipGetLastError();
     }
 };
@@ -1139,9 +1077,9 @@ static bool use_general(int max_len) { return !staged_takes(max_len); }
 hipError_t launch_single(const ScgSingleParams& P, int tmpl_len, const ScgReads& R, int64_t n, const ScgCounters& counts, int32_t* flag, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     if (use_general(R.max_len) || P.index.wide == 2) {
-        if (P.index.wide == 2) hipLaunchKernelGGL(single_kernel<Big>, dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R, n, counts);     // keys of 65..256 bases
-        else if (P.index.wide || P.scan.nreg != 1) hipLaunchKernelGGL(single_kernel<uint64_t>, dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R, n, counts);
-        else hipLaunchKernelGGL(single_kernel<uint32_t>, dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R, n, counts);
+        with_key(P.index.wide ? P.index.wide : (int)(P.scan.nreg != 1), [&](auto s) {     // (concatenated keys: 64 bits)
+            hipLaunchKernelGGL((single_kernel<typename decltype(s)::W>), dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R, n, counts);
+        });
         return hipGetLastError();
     }
     return dispatch_shape<LaunchSingle>(R.max_len, tmpl_len, P, R, n, counts, flag, stream);
@@ -1149,11 +1087,9 @@ hipError_t launch_single(const ScgSingleParams& P, int tmpl_len, const ScgReads&
 
 template<int NW, int NT> struct LaunchRandom {
     static hipError_t go(const ScgSingleParams& P, const ScgReads& R, int64_t n, int32_t* hits, int32_t* flag, hipStream_t stream) {
-        if (NW == 5 && P.scan.compact_ok && R.max_len - P.scan.len + 1 <= 96) {
-            hipLaunchKernelGGL((random_staged_kernel<NW, NT, (NW == 5 ? 3 : NW)>), dim3(staged_grid(n)), dim3(STAGE_BLOCK), extra_lds(), stream, P, R, n, hits, flag);
-        } else {
-            hipLaunchKernelGGL((random_staged_kernel<NW, NT, NW>), dim3(staged_grid(n)), dim3(STAGE_BLOCK), extra_lds(), stream, P, R, n, hits, flag);
-        }
+        with_shape<NW>(compact_fits<NW>(P.scan.compact_ok, R.max_len, P.scan.len), false, [&](auto s) {     // (no key: only the template is looked for)
+            hipLaunchKernelGGL((random_staged_kernel<NW, NT, decltype(s)::NC>), dim3(staged_grid(n)), dim3(STAGE_BLOCK), extra_lds(), stream, P, R, n, hits, flag);
+        });
         return hipGetLastError();
     }
 };
@@ -1170,9 +1106,9 @@ hipError_t launch_random(const ScgSingleParams& P, int tmpl_len, const ScgReads&
 hipError_t launch_combo(const ScgComboParams& P, int tmpl_len, const ScgReads& R, int64_t n, const ScgCounters& cells, int32_t* flag, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     if (use_general(R.max_len) || P.index[0].wide == 2) {
-        if (P.index[0].wide == 2) hipLaunchKernelGGL(combo_kernel<Big>, dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R, n, cells);
-        else if (P.index[0].wide) hipLaunchKernelGGL(combo_kernel<uint64_t>, dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R, n, cells);
-        else hipLaunchKernelGGL(combo_kernel<uint32_t>, dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R, n, cells);
+        with_key(P.index[0].wide, [&](auto s) {
+            hipLaunchKernelGGL((combo_kernel<typename decltype(s)::W>), dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R, n, cells);
+        });
         return hipGetLastError();
     }
     return dispatch_shape<LaunchCombo>(R.max_len, tmpl_len, P, R, n, cells, flag, stream);
@@ -1182,9 +1118,9 @@ hipError_t launch_dual(const ScgDualParams& P, int tmpl_len, const ScgReads& R1,
     if (n <= 0) return hipSuccess;
     const int lo_len = R1.max_len < R2.max_len ? R1.max_len : R2.max_len;
     if (use_general(lo_len) || use_general(R1.max_len > R2.max_len ? R1.max_len : R2.max_len) || P.index1.wide == 2) {
-        if (P.index1.wide == 2) hipLaunchKernelGGL(dual_kernel<Big>, dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R1, R2, n, counts);
-        else if (P.index1.wide) hipLaunchKernelGGL(dual_kernel<uint64_t>, dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R1, R2, n, counts);
-        else hipLaunchKernelGGL(dual_kernel<uint32_t>, dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R1, R2, n, counts);
+        with_key(P.index1.wide, [&](auto s) {
+            hipLaunchKernelGGL((dual_kernel<typename decltype(s)::W>), dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R1, R2, n, counts);
+        });
         return hipGetLastError();
     }
     const int max_len = R1.max_len > R2.max_len ? R1.max_len : R2.max_len;
@@ -1353,9 +1289,9 @@ hipError_t launch_fold(int32_t* replicas, int shift, int64_t n, int32_t* counter
 hipError_t launch_match(const ScgIndex& tab, const uint8_t* d_seqs, int32_t n, int cap, int reverse,
                         int32_t* d_index, int32_t* d_mm, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    if (tab.wide == 2) hipLaunchKernelGGL(match_kernel<Big>, dim3(grid_for(n)), dim3(BLOCK), 0, stream, tab, d_seqs, n, cap, reverse, d_index, d_mm);
-    else if (tab.wide) hipLaunchKernelGGL(match_kernel<uint64_t>, dim3(grid_for(n)), dim3(BLOCK), 0, stream, tab, d_seqs, n, cap, reverse, d_index, d_mm);
-    else hipLaunchKernelGGL(match_kernel<uint32_t>, dim3(grid_for(n)), dim3(BLOCK), 0, stream, tab, d_seqs, n, cap, reverse, d_index, d_mm);
+    with_key(tab.wide, [&](auto s) {
+        hipLaunchKernelGGL((match_kernel<typename decltype(s)::W>), dim3(grid_for(n)), dim3(BLOCK), 0, stream, tab, d_seqs, n, cap, reverse, d_index, d_mm);
+    });
     return hipGetLastError();
 }
 

@@ -15,7 +15,8 @@
 //           (position-major, forward before reverse: kaori/SimpleSingleMatch.hpp:226-242); each is
 //           verified exactly against the template planes (XOR/AND/popcount over the window taken
 //           from LDS), its variable region is cut out of the planes and matched through the
-//           segment index (scg_engine.hip.h).
+//           segment index (scg_engine.hip.h).  The walk itself is next_candidate() below, over one
+//           strand's mask or over both.
 //
 // The host picks NW / NT from the batch's maximum read length and the template length, so every
 // read fits its tile row; batches with reads longer than 320 bases (or of unknown maximum length)
@@ -469,6 +470,14 @@ struct StagedRead {
     int n;        // length
 };
 
+// Read `rd` of R in a tile that stage_reads filled from byte `span0` on.
+__device__ __forceinline__ StagedRead staged_read(const ScgReads& R, const Read& rd, int64_t span0) {
+    StagedRead sr;
+    sr.bit = (int)((int64_t)(rd.p - R.seqs) - span0);
+    sr.n = rd.n;
+    return sr;
+}
+
 // The last window position of a read of n bases for a template of tlen: candidates beyond it are not candidates
 // (seed_candidates leaves them in its masks).  Negative when the read is shorter than the template.
 __device__ __forceinline__ int last_position(int n, int tlen) { return n - tlen; }
@@ -505,6 +514,52 @@ __device__ __forceinline__ void scan_read(const Tile<NW>& tile, const StagedRead
 #pragma unroll
         for (int i = 0; i < NC; ++i) candR[i] = 0;
     }
+}
+
+// Phase C's walk over one strand's candidates, in ascending order: takes the lowest position out of the mask and hands it
+// back as `p`; false once nothing is left at or below `last` (an empty mask gives 1 << 30).
+template<int NC>
+__device__ __forceinline__ bool next_candidate(uint32_t cand[NC], int last, int& p) {
+    p = first_bit<NC>(cand);
+    if (p > last) return false;
+    clear_bit<NC>(cand, p);
+    return true;
+}
+
+// The same over both strands, in the reference's order: position-major, forward first on ties.
+template<int NC>
+__device__ __forceinline__ bool next_candidate(uint32_t candF[NC], uint32_t candR[NC], int last, int& p, bool& rev) {
+    const int pf = first_bit<NC>(candF), pr = first_bit<NC>(candR);
+    rev = pr < pf;
+    p = rev ? pr : pf;
+    if (p > last) return false;
+    clear_bit<NC>(candF, rev ? -1 : p);
+    clear_bit<NC>(candR, rev ? p : -1);
+    return true;
+}
+
+// The read (or pair) of this lane: workgroup b takes reads [b * STAGE_BLOCK, (b + 1) * STAGE_BLOCK).
+__device__ __forceinline__ int64_t lane_read() { return (int64_t)blockIdx.x * STAGE_BLOCK + threadIdx.x; }
+
+// What a lane of a one-tile kernel (single, random, combination) finds after staging.
+enum class Lane { idle, unstaged, ready };
+
+// Phase A of the one-tile kernels, barrier included: EVERY lane of the workgroup calls this.  `idle`: no read for this
+// lane.  `unstaged`: the workgroup's span or this lane's read does not fit the tile.  The host picks the tile shape from
+// the batch's maximum read length, so that bound was wrong: the caller flags it (reported by scg_plan_read) instead of
+// guessing.  `ready`: `sr` is the lane's read (lane_read()).
+template<int NW, int NT>
+__device__ __forceinline__ Lane stage_tile(const ScgScan& T, const ScgReads& R, int64_t n_reads, Tile<NW>& tile, StagedRead& sr) {
+    const int64_t r0 = (int64_t)blockIdx.x * STAGE_BLOCK;
+    const int nr = (int)((n_reads - r0) < STAGE_BLOCK ? (n_reads - r0) : STAGE_BLOCK);
+    int64_t span0 = 0;
+    const bool staged = (T.len <= 32 * NT) && stage_reads<NW>(R, n_reads, r0, nr, tile, span0);
+    __syncthreads();
+    if ((int)threadIdx.x >= nr) return Lane::idle;
+    const Read rd = get_read(R, r0 + threadIdx.x);
+    if (!staged || rd.n > 32 * NW) return Lane::unstaged;
+    sr = staged_read(R, rd, span0);
+    return Lane::ready;
 }
 
 } // namespace scgdev
