@@ -129,6 +129,19 @@ int scg_count_dual_barcodes(const char* path1, const char* constant1, int revers
                             int32_t* counts_out, int32_t* total_out,
                             char* err, size_t errcap);
 
+/* One barcode library sequenced paired-end, the construct on either mate: kaori::SingleBarcodePairedEnd
+ * (inst/include/kaori/handlers/SingleBarcodePairedEnd.hpp:93-124), the one handler of the reference's headers that its
+ * src/ does not call.  Template, strand, pool and mismatches as in scg_count_single_barcodes, for both mates.  Pair i is
+ * read i of path1 and read i of path2.  use_first: the first match of mate 1, else of mate 2.  Otherwise the best match
+ * of each mate; the mate with fewer mismatches counts, equal mismatches count once when both mates name the same
+ * barcode and not at all when they differ.  counts_out[n_pool]; *total_out the number of pairs.  Both readers are opened
+ * before the arguments are checked; files of different lengths give "different number of reads in paired FASTQ files". */
+int scg_count_single_barcodes_paired(const char* path1, const char* path2, const char* constant, int strand,
+                                     const char* const* pool, int32_t n_pool,
+                                     int mismatches, int use_first, int nthreads,
+                                     int32_t* counts_out, int32_t* total_out,
+                                     char* err, size_t errcap);
+
 /* countDualBarcodesSingleEnd hot path: every variable region of the construct lies in
  * one read; pools[r][c] over the regions r spells valid combination c.  Replaces
  * src/count_dual_barcodes_single_end.cpp:53-87, non-diagnostic branch (:27-34, kaori::DualBarcodesSingleEnd).
@@ -225,8 +238,9 @@ int scg_count_dual_barcodes_files(const char* const* paths1, const char* constan
                                   int32_t* counts_out, int32_t* totals_out,
                                   char* err, size_t errcap);
 
-/* The four entries below -- matrixOfDualBarcodes(include.invalid=TRUE), matrixOfDualBarcodesSingleEnd with and without
- * include.invalid (R/countDualBarcodesSingleEnd.R) and matrixOfPairedComboBarcodes (R/countPairedComboBarcodes.R) -- keep
+/* The five entries below -- matrixOfDualBarcodes(include.invalid=TRUE), matrixOfDualBarcodesSingleEnd with and without
+ * include.invalid (R/countDualBarcodesSingleEnd.R), matrixOfPairedComboBarcodes (R/countPairedComboBarcodes.R) and the
+ * paired single-barcode handler, which has no R function -- keep
  * the contract above and state the rest of it: argument errors are SCG_ERR_INVALID (SCG_ERR_UNSUPPORTED) with the message
  * of the one-file entry, raised before any file is opened and any device is touched; n_files == 0 succeeds and writes
  * nothing; where an entry has per-file malloc'd outputs (arrays of n_files entries as in
@@ -261,6 +275,15 @@ int scg_count_dual_barcodes_single_end_diagnostics_files(const char* const* path
                                                          int strand, int mismatches, int use_first, int nthreads,
                                                          int32_t* counts_out, int32_t** invalid_indices_out, int32_t** invalid_freq_out,
                                                          int64_t* k_out, int32_t* totals_out, char* err, size_t errcap);
+
+/* Per file what scg_count_single_barcodes_paired gives (kaori::SingleBarcodePairedEnd, SingleBarcodePairedEnd.hpp:93-124).
+ * counts_out: n_pool x n_files, column-major; totals_out: n_files. */
+int scg_count_single_barcodes_paired_files(const char* const* paths1, const char* const* paths2, int32_t n_files,
+                                           const char* constant, int strand,
+                                           const char* const* pool, int32_t n_pool,
+                                           int mismatches, int use_first, int nthreads,
+                                           int32_t* counts_out, int32_t* totals_out,
+                                           char* err, size_t errcap);
 
 /* indices_out / freq_out / k_out: per file, as scg_count_combo_barcodes_paired returns them (release every entry with
  * scg_free); totals_out, barcode1_only_out, barcode2_only_out: n_files entries each. */
@@ -360,6 +383,12 @@ int scg_plan_single(scg_plan** plan_out, const char* constant, int strand,
                     const char* const* pool, int32_t n_pool, int mismatches, int use_first,
                     int device, char* err, size_t errcap);
 
+/* Plan for kaori::SingleBarcodePairedEnd (handlers/SingleBarcodePairedEnd.hpp:93-124): scg_plan_single's arguments, checks
+ * and counters; counted with scg_count_batch_paired (pair i = read i of both batches), read with scg_plan_read. */
+int scg_plan_single_paired(scg_plan** plan_out, const char* constant, int strand,
+                           const char* const* pool, int32_t n_pool, int mismatches, int use_first,
+                           int device, char* err, size_t errcap);
+
 int scg_plan_combo(scg_plan** plan_out, const char* constant, int strand,
                    const char* const* pool0, int32_t n_pool0,
                    const char* const* pool1, int32_t n_pool1,
@@ -433,7 +462,8 @@ int scg_plan_reset(scg_plan* plan, void* stream, char* err, size_t errcap);
 int scg_count_batch(scg_plan* plan, const char* d_seqs, const uint32_t* d_offsets, int32_t fixed_len,
                     int32_t max_len, int64_t n_reads, void* stream, char* err, size_t errcap);
 
-/* Same for read pairs (dual plans); pair i is (read i of batch 1, read i of batch 2). */
+/* Same for read pairs (dual, paired-combination and paired single-barcode plans); pair i is (read i of batch 1, read i of
+ * batch 2). */
 int scg_count_batch_paired(scg_plan* plan,
                            const char* d_seqs1, const uint32_t* d_offsets1, int32_t fixed_len1,
                            const char* d_seqs2, const uint32_t* d_offsets2, int32_t fixed_len2,

@@ -13,7 +13,7 @@ from .api import (  # noqa: F401
     count_single_barcodes, count_combo_barcodes_single, count_dual_barcodes, count_combo_barcodes_paired,
     count_single_barcodes_files, count_combo_barcodes_single_files, count_dual_barcodes_files, count_dual_barcodes_single_end,
     count_dual_barcodes_diagnostics_files, count_dual_barcodes_single_end_files, count_dual_barcodes_single_end_diagnostics_files,
-    count_combo_barcodes_paired_files, count_random_barcodes, count_random_barcodes_files, match_barcodes, parse_fastq,
+    count_combo_barcodes_paired_files, count_single_barcodes_paired, count_single_barcodes_paired_files, count_random_barcodes, count_random_barcodes_files, match_barcodes, parse_fastq,
 )
 from .engine import Plan, combo_compact, upload_reads  # noqa: F401
 

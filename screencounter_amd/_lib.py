@@ -58,6 +58,10 @@ SIGNATURES = {
     "scg_count_dual_barcodes": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, c_str_p,
                                           C.c_char_p, C.c_char_p, C.c_int, C.c_int, c_str_p, C.c_int32,
                                           C.c_int, C.c_int, C.c_int, C.c_int, i32_p, i32_p, C.c_char_p, C.c_size_t]),
+    "scg_count_single_barcodes_paired": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, c_str_p, C.c_int32, C.c_int, C.c_int, C.c_int,
+                                                   i32_p, i32_p, C.c_char_p, C.c_size_t]),
+    "scg_count_single_barcodes_paired_files": (C.c_int, [c_str_p, c_str_p, C.c_int32, C.c_char_p, C.c_int, c_str_p, C.c_int32,
+                                                         C.c_int, C.c_int, C.c_int, i32_p, i32_p, C.c_char_p, C.c_size_t]),
     "scg_match_barcodes": (C.c_int, [c_str_p, C.c_int32, c_str_p, C.c_int32, C.c_int, C.c_int, i32_p, i32_p, C.c_char_p, C.c_size_t]),
     "scg_count_single_barcodes_files": (C.c_int, [c_str_p, C.c_int32, C.c_char_p, C.c_int, c_str_p, C.c_int32, C.c_int, C.c_int, C.c_int,
                                                   i32_p, i32_p, C.c_char_p, C.c_size_t]),
@@ -94,6 +98,8 @@ SIGNATURES = {
     "scg_parse_fastq": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), i64_p, C.c_char_p, C.c_size_t]),
     "scg_plan_single": (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, c_str_p, C.c_int32, C.c_int, C.c_int, C.c_int,
                                   C.c_char_p, C.c_size_t]),
+    "scg_plan_single_paired": (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, c_str_p, C.c_int32, C.c_int, C.c_int, C.c_int,
+                                         C.c_char_p, C.c_size_t]),
     "scg_plan_combo": (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, c_str_p, C.c_int32, c_str_p, C.c_int32, C.c_int, C.c_int,
                                  C.c_int, C.c_char_p, C.c_size_t]),
     "scg_plan_dual": (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, C.c_int, c_str_p, C.c_char_p, C.c_int, C.c_int, c_str_p,

@@ -179,6 +179,41 @@ def count_dual_barcodes_files(paths1: Sequence[str], constant1: str, reverse1: b
     return _files_matrix(counts, len(pool1), n), [int(totals[i]) for i in range(n)]
 
 
+def count_single_barcodes_paired(path1: str, path2: str, constant: str, strand: int, pool: Sequence[str], mismatches: int, use_first: bool,
+                                 nthreads: int = 1):
+    """kaori::SingleBarcodePairedEnd (handlers/SingleBarcodePairedEnd.hpp:93-124) over two files: the barcode of a pair is
+    looked for on either mate -> (counts int32[len(pool)], total pairs)."""
+    L = _lib.load()
+    counts = np.zeros(max(len(pool), 1), dtype=np.int32)
+    total = C.c_int32(0)
+    err = errbuf()
+    parr, _keep = cstr_array(pool)
+    check(L.scg_count_single_barcodes_paired(os.fspath(path1).encode(), os.fspath(path2).encode(), constant.encode(), int(strand), parr,
+                                             len(pool), int(mismatches), int(bool(use_first)), int(nthreads),
+                                             counts.ctypes.data_as(_lib.i32_p), C.byref(total), err, _lib.ERRCAP), err)
+    return counts[:len(pool)].copy(), int(total.value)
+
+
+def count_single_barcodes_paired_files(paths1: Sequence[str], paths2: Sequence[str], constant: str, strand: int, pool: Sequence[str],
+                                       mismatches: int, use_first: bool, nthreads: int = 1, devices=None):
+    """scg_count_single_barcodes_paired_files -> (counts int32[len(pool), n_files], totals list)."""
+    if len(paths1) != len(paths2):
+        raise ValueError("paths1 and paths2 differ in length")
+    L = _lib.load()
+    n = len(paths1)
+    counts = np.zeros((max(n, 1), max(len(pool), 1)), dtype=np.int32)
+    totals = (C.c_int32 * max(n, 1))()
+    err = errbuf()
+    parr, _keep = cstr_array(pool)
+    f1, _fk1 = cstr_array([os.fspath(x) for x in paths1])
+    f2, _fk2 = cstr_array([os.fspath(x) for x in paths2])
+    with _devices_env(devices):
+        check(L.scg_count_single_barcodes_paired_files(f1, f2, n, constant.encode(), int(strand), parr, len(pool), int(mismatches),
+                                                       int(bool(use_first)), int(nthreads), _files_out(counts, len(pool)), totals,
+                                                       err, _lib.ERRCAP), err)
+    return _files_matrix(counts, len(pool), n), [int(totals[i]) for i in range(n)]
+
+
 def count_dual_barcodes_diagnostics_files(paths1: Sequence[str], constant1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],
                                           paths2: Sequence[str], constant2: str, reverse2: bool, mismatches2: int, pool2: Sequence[str],
                                           randomized: bool, use_first: bool, nthreads: int = 1, devices=None):

@@ -196,6 +196,13 @@ int scg_plan_single(scg_plan** plan_out, const char* constant, int strand, const
     });
 }
 
+int scg_plan_single_paired(scg_plan** plan_out, const char* constant, int strand, const char* const* pool, int32_t n_pool,
+                           int mismatches, int use_first, int device, char* err, size_t errcap) {
+    return new_plan(plan_out, device, err, errcap, [&] {
+        return compile_single_paired(constant, strand, pool, n_pool, mismatches, use_first);
+    });
+}
+
 int scg_plan_combo(scg_plan** plan_out, const char* constant, int strand, const char* const* pool0, int32_t n_pool0,
                    const char* const* pool1, int32_t n_pool1, int mismatches, int use_first,
                    int device, char* err, size_t errcap) {
@@ -289,6 +296,7 @@ int scg_count_batch(scg_plan* plan, const char* d_seqs, const uint32_t* d_offset
     return guarded(err, errcap, [&] {
         if (!plan) throw Error(SCG_ERR_INVALID, "null plan");
         if (plan->kind == scg_plan::DUAL) throw Error(SCG_ERR_INVALID, "scg_count_batch called on a dual plan; use scg_count_batch_paired");
+        if (plan->kind == scg_plan::SINGLE_PAIRED) throw Error(SCG_ERR_INVALID, "scg_count_batch called on a paired single-barcode plan; use scg_count_batch_paired");
         check_reads_args(d_seqs, d_offsets, fixed_len, n_reads);
         DeviceGuard g(plan->device);
         launch_batch(plan, make_reads(d_seqs, d_offsets, fixed_len, max_len), n_reads, static_cast<hipStream_t>(stream));
@@ -300,7 +308,7 @@ int scg_count_batch_paired(scg_plan* plan, const char* d_seqs1, const uint32_t* 
                            int64_t n_pairs, void* stream, char* err, size_t errcap) {
     return guarded(err, errcap, [&] {
         if (!plan) throw Error(SCG_ERR_INVALID, "null plan");
-        if (plan->kind != scg_plan::DUAL) throw Error(SCG_ERR_INVALID, "scg_count_batch_paired needs a dual plan");
+        if (plan->kind != scg_plan::DUAL && plan->kind != scg_plan::SINGLE_PAIRED) throw Error(SCG_ERR_INVALID, "scg_count_batch_paired needs a dual plan");
         check_reads_args(d_seqs1, d_offsets1, fixed_len1, n_pairs);
         check_reads_args(d_seqs2, d_offsets2, fixed_len2, n_pairs);
         DeviceGuard g(plan->device);
@@ -411,6 +419,21 @@ int scg_count_dual_barcodes(const char* path1, const char* constant1, int revers
         }
         auto set = compile_and_count_paired(path1, path2, fq1, fq2, nthreads, [&] {
             return compile_dual(constant1, reverse1, mismatches1, pool1, constant2, reverse2, mismatches2, pool2, n_pool, randomized, use_first);
+        });
+        result_counts(set->all(), counts_out, total_out);
+    });
+}
+
+// kaori::SingleBarcodePairedEnd over two files: both readers first, as scg_count_dual_barcodes.
+int scg_count_single_barcodes_paired(const char* path1, const char* path2, const char* constant, int strand, const char* const* pool, int32_t n_pool,
+                                     int mismatches, int use_first, int nthreads, int32_t* counts_out, int32_t* total_out,
+                                     char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (!path1 || !path2 || !counts_out || !total_out) throw Error(SCG_ERR_INVALID, "null argument");
+        scg::FastqStream fq1(path1);
+        scg::FastqStream fq2(path2);
+        auto set = compile_and_count_paired(path1, path2, fq1, fq2, nthreads, [&] {
+            return compile_single_paired(constant, strand, pool, n_pool, mismatches, use_first);
         });
         result_counts(set->all(), counts_out, total_out);
     });
@@ -564,9 +587,9 @@ int scg_count_dual_barcodes_files(const char* const* paths1, const char* constan
     });
 }
 
-// The four entries below check their arguments -- the template and the pools are compiled, host work only -- before any
+// The five entries below check their arguments -- the template and the pools are compiled, host work only -- before any
 // file is opened and any device is touched; then every device gets its plan and takes the files one at a time.  In all
-// seven many-files entries with a library a plan starts every file from reset_plan (counters, sparse combinations, runs in
+// eight many-files entries with a library a plan starts every file from reset_plan (counters, sparse combinations, runs in
 // flight, the oversize-read flag), and a file's outputs are read by the function its one-file entry reads them with
 // (result_counts, result_combinations, result_diagnostics).
 
@@ -591,6 +614,22 @@ int scg_count_dual_barcodes_diagnostics_files(const char* const* paths1, const c
                 result_diagnostics(std::vector<scg_plan*>(1, P), counts_out + stride * static_cast<size_t>(f), &invalid_indices_out[f], &invalid_freq_out[f],
                                    &k_out[f], &totals_out[f], &barcode1_only_out[f], &barcode2_only_out[f]);
             });
+        });
+    });
+}
+
+int scg_count_single_barcodes_paired_files(const char* const* paths1, const char* const* paths2, int32_t n_files, const char* constant, int strand,
+                                           const char* const* pool, int32_t n_pool, int mismatches, int use_first, int nthreads,
+                                           int32_t* counts_out, int32_t* totals_out, char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (n_files < 0 || (n_files > 0 && (!paths1 || !paths2 || !totals_out || (n_pool > 0 && !counts_out)))) throw Error(SCG_ERR_INVALID, "null argument");
+        for (int32_t f = 0; f < n_files; ++f) if (!paths1[f] || !paths2[f]) throw Error(SCG_ERR_INVALID, "null argument");
+        if (n_files == 0) return;
+        auto compiled = compile_single_paired(constant, strand, pool, n_pool, mismatches, use_first);
+        PlanSet set(std::move(compiled), devices_for_files(n_files));
+        const size_t stride = static_cast<size_t>(n_pool);
+        schedule_paired(n_files, set, paths1, paths2, nthreads, [&](scg_plan* P, int32_t f) {
+            result_counts(std::vector<scg_plan*>(1, P), counts_out + stride * static_cast<size_t>(f), &totals_out[f]);
         });
     });
 }

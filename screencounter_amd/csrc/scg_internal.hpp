@@ -258,7 +258,9 @@ struct RandomTally {
 };
 
 struct scg_plan {
-    enum Kind { SINGLE, COMBO, DUAL, DUAL_SE_DIAG, RANDOM } kind = SINGLE;   // DUAL_SE_DIAG: single-end dual barcodes, include.invalid=TRUE
+    // DUAL_SE_DIAG: single-end dual barcodes, include.invalid=TRUE; SINGLE_PAIRED: one barcode on either mate of a pair
+    // (kaori::SingleBarcodePairedEnd) -- a single plan in everything but the batches it takes
+    enum Kind { SINGLE, COMBO, DUAL, DUAL_SE_DIAG, RANDOM, SINGLE_PAIRED } kind = SINGLE;
     int device = 0;
 
     // host-compiled pieces (valid before any device work)
@@ -324,7 +326,7 @@ struct scg_plan {
             d_tmpl2.upload(t2);
         }
         tab[0].upload(htab[0]);
-        if (kind != SINGLE) tab[1].upload(htab[1]);
+        if (kind != SINGLE && kind != SINGLE_PAIRED) tab[1].upload(htab[1]);
         if (kind == DUAL_SE_DIAG) { tab_combined.upload(htab_combined); htab_combined = scg::HostIndex(); }
         if (kind == DUAL) pairs.upload(hpairs);
         own_counters.alloc(static_cast<size_t>(std::max<int64_t>(n_counters, 1)) * sizeof(int32_t));   // (plans without counters: random barcodes)
@@ -383,6 +385,7 @@ int64_t dense_cells();
 ScgReads make_reads(const char* d_seqs, const uint32_t* d_offsets, int32_t fixed_len, int32_t max_len);
 void check_reads_args(const char* d_seqs, const uint32_t* d_offsets, int32_t fixed_len, int64_t n);
 std::unique_ptr<scg_plan> compile_single(const char* constant, int strand, const char* const* pool, int32_t n_pool, int mismatches, int use_first);
+std::unique_ptr<scg_plan> compile_single_paired(const char* constant, int strand, const char* const* pool, int32_t n_pool, int mismatches, int use_first);
 std::unique_ptr<scg_plan> compile_dual_single_end(const char* constant, int strand, const char* const* const* pools, const int32_t* n_pools, int32_t n_regions,
                                                   int mismatches, int use_first);
 std::unique_ptr<scg_plan> compile_combo(const char* constant, int strand, const char* const* pool0, int32_t n0, const char* const* pool1, int32_t n1, int mismatches,

@@ -8,6 +8,7 @@
 // kaori handler's process() (paths relative to inst/include/kaori/handlers/ in the reference):
 //   single_kernel <- SingleBarcodeSingleEnd::process          SingleBarcodeSingleEnd.hpp:93-104
 //                    + SimpleSingleMatch::search_first/best    ../SimpleSingleMatch.hpp:200-306
+//   single_paired_kernel <- SingleBarcodePairedEnd::process   SingleBarcodePairedEnd.hpp:93-124
 //   combo_kernel  <- CombinatorialBarcodesSingleEnd::process   CombinatorialBarcodesSingleEnd.hpp:149-258
 //   dual_kernel   <- DualBarcodesPairedEnd::process            DualBarcodesPairedEnd.hpp:228-381
 // Per-handler vector<int> counters + serial reduce() become device atomics on one int32 array.
@@ -85,6 +86,34 @@ struct BestPair {
     }
 };
 
+// SingleBarcodePairedEnd.hpp:93-122: one barcode, looked for on both mates of a pair.  Start from {0, -1, false} and offer
+// mate 1's search, then mate 2's.  use_first (:94-99): mate 1's hit, else mate 2's -- wants_second() says whether mate 2 is
+// searched at all.  Otherwise (:100-121) the mate with fewer mismatches; on equal mismatches the pair counts only when
+// both mates name the same barcode.
+struct BestMate {
+    int best, index;
+    bool found;
+    __device__ __forceinline__ bool wants_second(bool use_first) const { return !(use_first && found); }
+    // (idx, mism): what single_read / single_read_staged gave for the mate
+    __device__ __forceinline__ void offer(int idx, int mism) {
+        if (idx < 0) return;
+        if (!found || mism < best) {
+            found = true; best = mism; index = idx;
+        } else if (mism == best && idx != index) {
+            index = -1;
+        }
+    }
+    __device__ __forceinline__ int result() const { return found ? index : -1; }
+};
+
+// Mate `pass` (0 / 1) of a pair's two read sets, selected field by field: wave-uniform scalars.
+__device__ __forceinline__ ScgReads mate_reads(int pass, const ScgReads& R1, const ScgReads& R2) {
+    ScgReads R = ScgReads();
+    R.seqs = pass ? R2.seqs : R1.seqs; R.offsets = pass ? R2.offsets : R1.offsets;
+    R.fixed_len = pass ? R2.fixed_len : R1.fixed_len; R.max_len = pass ? R2.max_len : R1.max_len;
+    return R;
+}
+
 // Read (or pair) i matched barcode idx, or none (-1): to the index stream (ScgCounters::unit_index) or straight to its counter.
 __device__ __forceinline__ void emit_index(const ScgCounters& counts, int64_t i, int idx) {
     if (counts.unit_index) counts.unit_index[i] = idx;
@@ -124,8 +153,10 @@ __device__ __forceinline__ QueryT<W> pack_regions(const ScgTemplate* T, const ui
     return reverse ? reverse_complement(q, total_len) : q;
 }
 
+// `mismatches`, when asked for: those of the match returned (BestSingle::best; the paired handler's rule compares them
+// across mates).  Looked at only when the result is >= 0.
 template<class W = uint32_t>
-__device__ __forceinline__ int single_read(const ScgSingleParams& P, const Read& rd) {
+__device__ __forceinline__ int single_read(const ScgSingleParams& P, const Read& rd, int* mismatches = nullptr) {
     const ScgTemplate* T = P.tmpl;
     const int len = T->len;
     const int max_mm = P.max_mm;
@@ -139,10 +170,14 @@ __device__ __forceinline__ int single_read(const ScgSingleParams& P, const Read&
             int idx, d;
             index_match<W>(P.index, q, max_mm - c, idx, d);
             if (idx < 0) continue;
-            if (P.use_first) return idx;              // SimpleSingleMatch.hpp:207-224 (c + d <= max_mm by construction)
+            if (P.use_first) {                        // SimpleSingleMatch.hpp:207-224 (c + d <= max_mm by construction)
+                if (mismatches) *mismatches = c + d;
+                return idx;
+            }
             hit.offer(idx, c + d);
         }
     }
+    if (mismatches) *mismatches = hit.best;
     return hit.result();
 }
 
@@ -153,6 +188,24 @@ __global__ __launch_bounds__(BLOCK) void single_kernel(ScgSingleParams P, ScgRea
     if (i >= n_reads) return;
     Read rd = get_read(R, i);
     emit_index(counts, i, single_read<W>(P, rd));
+}
+
+// One barcode on either mate, byte-wise: one lane per pair, the two mates one after the other through the same search.
+template<class W>
+__global__ __launch_bounds__(BLOCK) void single_paired_kernel(ScgSingleParams P, ScgReads R1, ScgReads R2, int64_t n_pairs,
+                                                               ScgCounters counts) {
+    int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n_pairs) return;
+    BestMate hit{0, -1, false};
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {           // (one loop body: the search exists once in the code)
+        if (pass && !hit.wants_second(P.use_first != 0)) break;
+        const Read rd = get_read(mate_reads(pass, R1, R2), i);
+        int mism = 0;
+        const int idx = single_read<W>(P, rd, &mism);
+        hit.offer(idx, mism);
+    }
+    emit_index(counts, i, hit.result());
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -400,7 +453,8 @@ __global__ __launch_bounds__(BLOCK) void dual_kernel(ScgDualParams P, ScgReads R
 // W = uint32_t: one variable region of <= 32 bases (the hot configuration).  W = uint64_t: keys of up to
 // 64 bases, one region or several concatenated (wide barcodes, countDualBarcodesSingleEnd).
 template<int NW, int NT, int NC, class W>
-__device__ __forceinline__ int single_read_staged(const ScgSingleParams& P, const Tile<NW>& tile, const StrandTable<NT>& st, const StagedRead& sr, int ablate = 0) {
+__device__ __forceinline__ int single_read_staged(const ScgSingleParams& P, const Tile<NW>& tile, const StrandTable<NT>& st, const StagedRead& sr, int ablate = 0,
+                                                  int* mismatches = nullptr) {
     const ScgScan& T = P.scan;
     const int max_mm = P.max_mm;
     uint32_t candF[NC], candR[NC];
@@ -426,9 +480,13 @@ __device__ __forceinline__ int single_read_staged(const ScgSingleParams& P, cons
         int idx, d;
         index_match<W>(P.index, q, max_mm - c, idx, d);
         if (idx < 0) continue;
-        if (P.use_first) return idx;
+        if (P.use_first) {
+            if (mismatches) *mismatches = c + d;
+            return idx;
+        }
         hit.offer(idx, c + d);
     }
+    if (mismatches) *mismatches = hit.best;     // (as in single_read)
     return hit.result();
 }
 
@@ -455,6 +513,48 @@ __global__ __launch_bounds__(STAGE_BLOCK, SCG_SINGLE_WAVES) __attribute__((amdgp
     idx = single_read_staged<NW, NT, NC, W>(P, tile, strands, sr);
 #endif
     emit_index(counts, lane_read(), idx);
+}
+
+// One barcode on either mate, in two passes over ONE tile (as dual_passes_kernel): mate 1 is staged, searched and reduced
+// to BestMate's three registers, then mate 2 takes the same planes -- the LDS of single_staged_kernel.  EVERY lane of the
+// workgroup reaches every barrier, whatever it has found: nothing returns before the loop is through, and what a lane
+// does between the barriers hangs on `wanted` alone (idle lanes of the last tile, lanes with their first-mode hit from
+// mate 1).  A mate shorter than the template, or empty, has no candidate at or below its last position and finds nothing.
+template<int NW, int NT, int NC, class W>
+__global__ __launch_bounds__(STAGE_BLOCK, SCG_SINGLE_WAVES) __attribute__((amdgpu_num_sgpr(80))) void single_paired_staged_kernel(ScgSingleParams P, ScgReads R1, ScgReads R2, int64_t n_pairs,
+                                                                   ScgCounters counts, int32_t* __restrict__ error_flag) {
+    __shared__ Tile<NW> tile;
+    __shared__ StrandTable<NT> strands;
+    fill_strand_table<NT>(strands, P.scan);
+    const int64_t r0 = (int64_t)blockIdx.x * STAGE_BLOCK;
+    const int nr = (int)((n_pairs - r0) < STAGE_BLOCK ? (n_pairs - r0) : STAGE_BLOCK);
+    const bool fits = P.scan.len <= 32 * NT;
+    const bool lane = (int)threadIdx.x < nr;
+    BestMate hit{0, -1, false};
+    bool bad = !fits;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {           // (one loop body: the search exists once in the code)
+        const ScgReads R = mate_reads(pass, R1, R2);
+        int64_t span = 0;
+        if (pass) __syncthreads();                   // every lane is done with mate 1's planes
+        const bool ok = fits && stage_reads<NW>(R, n_pairs, r0, nr, tile, span);
+        __syncthreads();
+        bad = bad || !ok;
+        const bool wanted = lane && ok && !(pass && !hit.wants_second(P.use_first != 0));
+        if (wanted) {
+            const Read rd = get_read(R, r0 + threadIdx.x);
+            if (rd.n > 32 * NW) {
+                bad = true;
+            } else {
+                int mism = 0;
+                const int idx = single_read_staged<NW, NT, NC, W>(P, tile, strands, staged_read(R, rd, span), 0, &mism);
+                hit.offer(idx, mism);
+            }
+        }
+    }
+    if (!lane) return;
+    if (bad) { *error_flag = 1; return; }
+    emit_index(counts, r0 + threadIdx.x, hit.result());
 }
 
 template<int NW, int NT, int NC>
@@ -1004,6 +1104,17 @@ template<int NW, int NT> struct LaunchSingle {
         return hipGetLastError();
     }
 };
+template<int NW, int NT> struct LaunchSinglePaired {
+    static hipError_t go(const ScgSingleParams& P, const ScgReads& R1, const ScgReads& R2, int64_t n, const ScgCounters& counts, int32_t* flag, hipStream_t stream) {
+        const int max_len = R1.max_len > R2.max_len ? R1.max_len : R2.max_len;
+        const bool wide = P.index.wide || P.scan.nreg != 1;
+        with_shape<NW>(compact_fits<NW>(P.scan.compact_ok, max_len, P.scan.len), wide, [&](auto s) {
+            using S = decltype(s);
+            hipLaunchKernelGGL((single_paired_staged_kernel<NW, NT, S::NC, typename S::W>), dim3(staged_grid(n)), dim3(STAGE_BLOCK), extra_lds(), stream, P, R1, R2, n, counts, flag);
+        });
+        return hipGetLastError();
+    }
+};
 template<int NW, int NT> struct LaunchCombo {
     template<int NC, class W>
     static void run(const ScgComboParams& P, const ScgReads& R, int64_t n, const ScgCounters& cells, int32_t* flag, hipStream_t stream) {
@@ -1083,6 +1194,20 @@ hipError_t launch_single(const ScgSingleParams& P, int tmpl_len, const ScgReads&
         return hipGetLastError();
     }
     return dispatch_shape<LaunchSingle>(R.max_len, tmpl_len, P, R, n, counts, flag, stream);
+}
+
+// SingleBarcodePairedEnd: the tile shape and the candidate mask go by the longer mate; a batch with a mate the staged
+// kernels do not take (staged_takes) goes to the byte-wise kernel whole.
+hipError_t launch_single_paired(const ScgSingleParams& P, int tmpl_len, const ScgReads& R1, const ScgReads& R2, int64_t n, const ScgCounters& counts, int32_t* flag, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const int lo_len = R1.max_len < R2.max_len ? R1.max_len : R2.max_len, hi_len = R1.max_len > R2.max_len ? R1.max_len : R2.max_len;
+    if (use_general(lo_len) || use_general(hi_len) || P.index.wide == 2) {
+        with_key(P.index.wide ? P.index.wide : (int)(P.scan.nreg != 1), [&](auto s) {
+            hipLaunchKernelGGL((single_paired_kernel<typename decltype(s)::W>), dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R1, R2, n, counts);
+        });
+        return hipGetLastError();
+    }
+    return dispatch_shape<LaunchSinglePaired>(hi_len, tmpl_len, P, R1, R2, n, counts, flag, stream);
 }
 
 template<int NW, int NT> struct LaunchRandom {

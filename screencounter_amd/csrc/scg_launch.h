@@ -15,6 +15,9 @@ namespace scg {
 bool staged_takes(int max_len);
 
 hipError_t launch_single(const ScgSingleParams& P, int tmpl_len, const ScgReads& R, int64_t n, const ScgCounters& counts, int32_t* flag, hipStream_t stream);
+// kaori::SingleBarcodePairedEnd: the barcode of pair i is looked for on read i of R1 and of R2
+hipError_t launch_single_paired(const ScgSingleParams& P, int tmpl_len, const ScgReads& R1, const ScgReads& R2, int64_t n, const ScgCounters& counts, int32_t* flag,
+                                hipStream_t stream);
 // countRandomBarcodes: d_hits[i] = (position << 1) | reverse of read i's template hit, or -1
 hipError_t launch_random(const ScgSingleParams& P, int tmpl_len, const ScgReads& R, int64_t n, int32_t* d_hits, int32_t* flag, hipStream_t stream);
 hipError_t launch_combo(const ScgComboParams& P, int tmpl_len, const ScgReads& R, int64_t n, const ScgCounters& cells, int32_t* flag, hipStream_t stream);

@@ -129,6 +129,15 @@ std::unique_ptr<scg_plan> compile_single(const char* constant, int strand, const
     return P;
 }
 
+// kaori::SingleBarcodePairedEnd (handlers/SingleBarcodePairedEnd.hpp:41-58): the template, pool and checks of the
+// single-end handler; the pairs go through launch_batch_paired.
+std::unique_ptr<scg_plan> compile_single_paired(const char* constant, int strand, const char* const* pool, int32_t n_pool,
+                                                int mismatches, int use_first) {
+    std::unique_ptr<scg_plan> P = compile_single(constant, strand, pool, n_pool, mismatches, use_first);
+    P->kind = scg_plan::SINGLE_PAIRED;
+    return P;
+}
+
 // countDualBarcodesSingleEnd (kaori::DualBarcodesSingleEnd, handlers/DualBarcodesSingleEnd.hpp:66-123): one read
 // holds every variable region; pools[r][c] over r spells valid combination c, and the concatenation of a window's
 // regions is matched against the concatenated library with one shared mismatch budget.  Same kernels as the single
@@ -815,7 +824,23 @@ ScgScan searched_strand_first(const ScgScan& t, bool reverse) {
     return o;
 }
 
+// One batch of a single-barcode plan over pairs: the index stream and the tally when both mates are staged (use_tally),
+// the replicas otherwise.
+static void launch_batch_single_paired(scg_plan* P, const ScgReads& R1, const ScgReads& R2, int64_t n, hipStream_t stream) {
+    scg_plan::Timer timer(P, stream);
+    ScgCounters counts = plan_counters(P);
+    const bool staged = scg::staged_takes(std::min(R1.max_len, R2.max_len)) && scg::staged_takes(std::max(R1.max_len, R2.max_len)) && !general_only(P);
+    const bool tally = use_tally(P, n) && staged;
+    if (tally) counts.unit_index = index_stream(P, stream, n);
+    HIP_CHECK(scg::launch_single_paired(single_params(P, P->tab[0].view), P->ht1.t.len, R1, R2, n, counts, P->error_flag.as<int32_t>(), stream));
+    timer.stop();
+    if (tally) HIP_CHECK(scg::launch_tally(counts.unit_index, n, P->counters, P->n_counters, stream));
+    else fold_replicas(P, stream);
+    P->total += n;
+}
+
 void launch_batch_paired(scg_plan* P, const ScgReads& R1, const ScgReads& R2, int64_t n, hipStream_t stream) {
+    if (P->kind == scg_plan::SINGLE_PAIRED) { launch_batch_single_paired(P, R1, R2, n, stream); return; }
     scg_plan::Timer timer(P, stream);
     ScgDualParams dp = ScgDualParams();
     dp.scan1 = searched_strand_first(P->scan1, P->rev1); dp.scan2 = searched_strand_first(P->scan2, P->rev2);

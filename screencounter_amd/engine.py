@@ -80,6 +80,18 @@ class Plan:
         return cls(h.value, "single", (len(pool),), device)
 
     @classmethod
+    def single_paired(cls, template: str, strand: int, pool: Sequence[str], mismatches: int = 0, use_first: bool = True,
+                      device: int = -1) -> "Plan":
+        """One barcode on either mate of a pair (kaori::SingleBarcodePairedEnd): counted with count_paired(), read with read()."""
+        L = _lib.load()
+        h = C.c_void_p()
+        err = errbuf()
+        parr, _keep = cstr_array(pool)
+        check(L.scg_plan_single_paired(C.byref(h), template.encode(), int(strand), parr, len(pool), int(mismatches),
+                                       int(bool(use_first)), int(device), err, _lib.ERRCAP), err)
+        return cls(h.value, "single_paired", (len(pool),), device)
+
+    @classmethod
     def combo(cls, template: str, strand: int, pool0: Sequence[str], pool1: Sequence[str], mismatches: int = 0,
               use_first: bool = True, device: int = -1) -> "Plan":
         L = _lib.load()

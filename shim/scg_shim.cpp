@@ -199,6 +199,32 @@ Rcpp::List count_single_barcodes_files(Rcpp::CharacterVector paths, std::string 
     return Rcpp::List::create(counts, totals);
 }
 
+// kaori::SingleBarcodePairedEnd (handlers/SingleBarcodePairedEnd.hpp:93-124): no R/ wrapper in the reference; INTEGRATION.md has the .Call.
+//[[Rcpp::export(rng=false)]]
+Rcpp::List count_single_barcodes_paired(std::string path1, std::string path2, std::string constant, int strand, Rcpp::CharacterVector pool,
+                                        int mismatches, bool use_first, int nthreads) {
+    auto p = borrow(pool);
+    Rcpp::IntegerVector counts(pool.size());
+    int total = 0;
+    char err[1024];
+    check(scg_count_single_barcodes_paired(path1.c_str(), path2.c_str(), constant.c_str(), strand, p.data(), (int32_t)p.size(),
+                                           mismatches, use_first, nthreads, counts.begin(), &total, err, sizeof(err)), err);
+    return Rcpp::List::create(counts, total);
+}
+
+//[[Rcpp::export(rng=false)]]
+Rcpp::List count_single_barcodes_paired_files(Rcpp::CharacterVector paths1, Rcpp::CharacterVector paths2, std::string constant, int strand,
+                                              Rcpp::CharacterVector pool, int mismatches, bool use_first, int nthreads) {
+    if (paths1.size() != paths2.size()) Rcpp::stop("'paths1' and 'paths2' should be of the same length");
+    auto f1 = borrow(paths1), f2 = borrow(paths2), p = borrow(pool);
+    Rcpp::IntegerMatrix counts((int)pool.size(), paths1.size());    // column f = file f
+    Rcpp::IntegerVector totals(paths1.size());
+    char err[1024];
+    check(scg_count_single_barcodes_paired_files(f1.data(), f2.data(), (int32_t)f1.size(), constant.c_str(), strand, p.data(), (int32_t)p.size(),
+                                                 mismatches, use_first, nthreads, counts.begin(), totals.begin(), err, sizeof(err)), err);
+    return Rcpp::List::create(counts, totals);
+}
+
 //[[Rcpp::export(rng=false)]]
 Rcpp::List count_combo_barcodes_single_files(Rcpp::CharacterVector paths, std::string constant, int strand, Rcpp::List pool,
                                              int mismatches, bool use_first, int nthreads) {

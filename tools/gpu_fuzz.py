@@ -13,6 +13,7 @@ import numpy as np  # noqa: E402
 import screencounter_amd as sc  # noqa: E402
 from oracle.pyoracle import Oracle, OracleError, write_fastq  # noqa: E402
 from tests import gen  # noqa: E402
+from tests import single_paired_ref  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 10_000
@@ -34,6 +35,16 @@ def one(kind, rng, tmp):
             p.count(s, o)
             got = p.read()
         assert got[1] == exp[1] and same(got[0], exp[0]), c
+    elif kind == "single_paired":          # against the composed reference (tests/single_paired_ref.py)
+        c = single_paired_ref.paired_case(rng, max_vlen=64, sizes=(1, 30, 60))
+        args = (c["template"], c["strand"], c["pool"], c["mismatches"], c["use_first"])
+        exp = single_paired_ref.count_single_paired(ora, c["reads1"], c["reads2"], *args)
+        s1, o1 = sc.upload_reads(c["reads1"], dev)
+        s2, o2 = sc.upload_reads(c["reads2"], dev)
+        with sc.Plan.single_paired(*args) as p:
+            p.count_paired(s1, s2, o1, o2)
+            got = p.read()
+        assert got[1] == exp[1] and same(got[0][:len(c["pool"])], exp[0]), c
     elif kind == "combo":
         c = gen.random_combo_case(rng)
         exp = ora.count_combo(c["reads"], c["template"], c["strand"], c["pool0"], c["pool1"], c["mismatches"], c["use_first"])
@@ -88,7 +99,7 @@ def one(kind, rng, tmp):
         assert same(got[0], exp[0]) and same(got[1], exp[1]), c
 
 
-kinds = ["single", "combo", "dual", "dual_diag", "paired_combo", "dual_se", "dual_se_diag", "random", "match"]
+kinds = ["single", "single_paired", "combo", "dual", "dual_diag", "paired_combo", "dual_se", "dual_se_diag", "random", "match"]
 t0 = last = time.time()
 it = 0
 with tempfile.TemporaryDirectory() as tmp:
