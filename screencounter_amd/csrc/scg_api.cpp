@@ -767,8 +767,7 @@ int scg_match_barcodes(const char* const* sequences, int32_t n_sequences, const 
             throw Error(SCG_ERR_INVALID, "null argument");
         }
         int clen = scg::pool_length(choices, n_choices);                     // src/match_barcodes.cpp:12
-        scg::HostIndex ht = clen > SCG_MAX_BARCODE ? scg::build_index_wide(choices, n_choices, clen, substitutions < 0 ? 0 : substitutions)
-                                                   : scg::build_index(choices, n_choices, clen, substitutions < 0 ? 0 : substitutions);   // :13
+        scg::HostIndex ht = scg::build_index(choices, n_choices, clen, substitutions < 0 ? 0 : substitutions, scg::key_class(clen));   // :13
         int slen = scg::pool_length(sequences, n_sequences);                 // :20
         if (n_sequences > 0 && slen != clen) {
             throw Error(SCG_ERR_INVALID, "sequences should have the same length as the choices (" + std::to_string(clen) + ")");

@@ -34,41 +34,36 @@ HostTemplate parse_template(const char* constant, int strand);
 // ---------------------------------------------------------------------------------------------
 int pool_length(const char* const* pool, int32_t n);   // throws if lengths differ
 
+// Key classes: 0 = up to 32 bases (2 x 32-bit planes), 1 = up to 64 ("wide"), 2 = up to 256 ("big"), the longest a template
+// can be (src/count_single_barcodes.cpp:37-47).  Pools that meet in one kernel (both regions of a combination, both mates
+// of a pair) are built in the widest class among them; concatenated multi-region keys are never narrow.
+inline int key_class(int len) { return len > SCG_MAX_WIDE_BARCODE ? 2 : (len > SCG_MAX_BARCODE ? 1 : 0); }
+
+// A node or slot is {key lo, key hi, value, next} in class 0, {lo64, hi64, value, next, 0, 0} in class 1 and
+// {lo x 4, hi x 4, value, next, 0, 0} (as 64-bit words) in class 2: 4, 8 and 20 32-bit words (ScgIndex).
 struct HostIndex {
     int32_t len = 0;
     int32_t n_entries = 0;
     int32_t nseg = 0;
-    int wide = 0;                    // 1: 2 x 64-bit planes, 8 words per node / slot; 2: 2 x 256-bit planes, 20 words (ScgIndex::wide)
+    int wide = 0;                    // the key class (ScgIndex::wide)
     uint32_t slot_mask = 0;
     int32_t nwalk[4] = {0, 0, 0, 0};
     uint64_t segmask[SCG_MAX_SEGMENTS] = {0, 0, 0, 0, 0, 0};
-    std::vector<uint32_t> nodes;     // [max(nseg,1)][n_entries] x 4 words: key lo, key hi, value, next in table s's chain
-    std::vector<uint32_t> tables;    // [nseg][slot_mask + 1] x 4 words: head node of the chain keyed in that slot
+    std::vector<uint32_t> nodes;     // [max(nseg,1)][n_entries] nodes, `next` being the next entry in table s's chain
+    std::vector<uint32_t> tables;    // [nseg][slot_mask + 1] slots: head node of the chain keyed in that slot
 };
 
-// max_mm is the plan's mismatch budget for this pool: the index gets max_mm + 1 segments
-// (none, i.e. dense scans, when that exceeds SCG_MAX_SEGMENTS).
+// The index of a pool of `len` bases in key class `cls` >= key_class(len).  max_mm is the plan's mismatch budget for this
+// pool: the index gets max_mm + 1 segments (none, i.e. dense scans, when that exceeds SCG_MAX_SEGMENTS).
 // value = barcode index; two barcodes sharing one concrete sequence => Error("duplicate sequences
 // detected (a, b) when constructing the trie").
-HostIndex build_index(const char* const* pool, int32_t n, int32_t len, int max_mm);
+HostIndex build_index(const char* const* pool, int32_t n, int32_t len, int max_mm, int cls);
 
-// Same for keys of up to 64 bases (wide index; always used for concatenated multi-region keys) and, beyond, of up to 256
-// bases (big index) -- the longest a template can be (src/count_single_barcodes.cpp:37-47).
-HostIndex build_index_wide(const char* const* pool, int32_t n, int32_t len, int max_mm);
-// The big index whatever the length (a pool that shares a kernel with a pool of more than 64 bases).
-HostIndex build_index_big(const char* const* pool, int32_t n, int32_t len, int max_mm);
-HostIndex build_uid_index_big(const char* const* pool, int32_t n, int32_t len, int max_mm,
-                              std::vector<std::vector<int32_t> >& expansions, size_t& n_uid);
-
-// value = uid of the concrete sequence (duplicates within the pool merge).  expansions[i] receives
-// the uids of barcode i's concrete expansions, in lexicographic (A,C,G,T) order.
-HostIndex build_uid_index(const char* const* pool, int32_t n, int32_t len, int max_mm,
-                          std::vector<std::vector<int32_t> >& expansions,
-                          std::vector<uint64_t>& uid_keys);
-
-// The same with wide keys (either pool of a pair longer than 32 bases); n_uid receives the number of distinct sequences.
-HostIndex build_uid_index_wide(const char* const* pool, int32_t n, int32_t len, int max_mm,
-                               std::vector<std::vector<int32_t> >& expansions, size_t& n_uid);
+// value = uid of the concrete sequence (duplicates within the pool merge; n_entries is the number of uids).
+// expansions[i] receives the uids of barcode i's concrete expansions, in lexicographic (A,C,G,T) order; uid_keys the key of
+// every uid in class 0 (for the pair table's dense list), nothing in the others.
+HostIndex build_uid_index(const char* const* pool, int32_t n, int32_t len, int max_mm, int cls,
+                          std::vector<std::vector<int32_t> >& expansions, std::vector<uint64_t>& uid_keys);
 
 struct HostPairTable {
     int32_t n_entries = 0;

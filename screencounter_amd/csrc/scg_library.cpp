@@ -4,13 +4,12 @@
 #include "scg_host.h"
 
 #include <algorithm>
-#include <array>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
 #include <mutex>
 #include <thread>
-#include <unordered_map>
+#include <string>
 
 namespace scg {
 
@@ -74,30 +73,70 @@ inline int iupac_codes(char c, int out[4]) {
 
 const int64_t MAX_EXPANSIONS = int64_t(1) << 26;
 
+// ---------------------------------------------------------------------------------------------
+// The key classes (scg_host.h: key_class).  A class says how a key is held on the host, how it lies in a node or slot of
+// the index -- WORDS 32-bit words: the key, the value at VALUE, the chain link after it, zeros up to whole uint4 -- and how
+// a position group is applied to it and hashed (scg_common.h: ScgIndex; the device does the same in KeyOps).
+// ---------------------------------------------------------------------------------------------
+struct Narrow {                 // up to 32 bases: both 32-bit planes in one word
+    typedef uint64_t Key;
+    static constexpr int CLS = 0, MAXLEN = SCG_MAX_BARCODE, WORDS = 4, VALUE = 2;
+    static void set_base(Key& k, int p, uint64_t code) { k |= ((code & 1) << p) | ((code >> 1) << (32 + p)); }    // plane-split (scg_common.h)
+    static void put_key(uint32_t* node, Key k) { node[0] = static_cast<uint32_t>(k); node[1] = static_cast<uint32_t>(k >> 32); }
+    // Turns the two position ranges of a group (as scg_big_group takes them) into the mask that masked() applies, and
+    // returns what ScgIndex::segmask holds for the group: here both are the plane-split mask.
+    static uint64_t group(uint64_t ranges, uint64_t mask[SCG_BIG_WORDS]) { scg_big_group(ranges, mask); mask[0] |= mask[0] << 32; return mask[0]; }
+    static Key masked(Key k, const uint64_t* mask) { return k & mask[0]; }
+    static uint32_t hash(Key k) { return scg_hash64(k); }
+};
+
+template<int N>
+struct PlaneKey {
+    uint64_t lo[N], hi[N];
+    bool operator==(const PlaneKey& o) const {
+        for (int w = 0; w < N; ++w) if (lo[w] != o.lo[w] || hi[w] != o.hi[w]) return false;
+        return true;
+    }
+};
+// N 64-bit words per plane: wide keys (N = 1: up to 64 bases, or several regions concatenated) and big keys
+// (N = SCG_BIG_WORDS: up to 256 bases, the longest a template can be).
+template<int N>
+struct Planes {
+    typedef PlaneKey<N> Key;
+    static constexpr int CLS = N == 1 ? 1 : 2, MAXLEN = 64 * N, WORDS = N == 1 ? 8 : 20, VALUE = 4 * N;
+    static void set_base(Key& k, int p, uint64_t code) { k.lo[p >> 6] |= (code & 1) << (p & 63); k.hi[p >> 6] |= (code >> 1) << (p & 63); }
+    static void put_key(uint32_t* node, const Key& k) {
+        for (int w = 0; w < N; ++w) {
+            node[2 * w] = static_cast<uint32_t>(k.lo[w]); node[2 * w + 1] = static_cast<uint32_t>(k.lo[w] >> 32);
+            node[2 * N + 2 * w] = static_cast<uint32_t>(k.hi[w]); node[2 * N + 2 * w + 1] = static_cast<uint32_t>(k.hi[w] >> 32);
+        }
+    }
+    // wide: the 64-bit position mask itself; big: the ranges (ScgIndex::segmask)
+    static uint64_t group(uint64_t ranges, uint64_t mask[SCG_BIG_WORDS]) { scg_big_group(ranges, mask); return N == 1 ? mask[0] : ranges; }
+    static Key masked(Key k, const uint64_t* mask) {
+        for (int w = 0; w < N; ++w) { k.lo[w] &= mask[w]; k.hi[w] &= mask[w]; }
+        return k;
+    }
+    static uint32_t hash(const Key& k) {
+        if constexpr (N == 1) return scg_hash128(k.lo[0], k.hi[0]); else return scg_hash_big(k.lo, k.hi);
+    }
+};
+
 // Calls f(key) for every concrete expansion of `s` in lexicographic (A,C,G,T) order.
-template<class F>
+template<class T, class F>
 void for_each_expansion(const char* s, int len, F f) {
-    int cnt[SCG_MAX_BARCODE], codes[SCG_MAX_BARCODE][4], choice[SCG_MAX_BARCODE];
+    int cnt[T::MAXLEN], codes[T::MAXLEN][4], choice[T::MAXLEN];
     bool plain = true;
-    uint64_t only = 0;
     for (int p = 0; p < len; ++p) {
         cnt[p] = iupac_codes(s[p], codes[p]);
         choice[p] = 0;
         plain &= cnt[p] == 1;
-        const uint64_t c = static_cast<uint64_t>(codes[p][0]);
-        only |= ((c & 1) << p) | ((c >> 1) << (32 + p));
-    }
-    if (plain) {            // the usual library: A, C, G, T only
-        f(only);
-        return;
     }
     for (;;) {
-        uint64_t key = 0;
-        for (int p = 0; p < len; ++p) {
-            uint64_t c = static_cast<uint64_t>(codes[p][choice[p]]);
-            key |= ((c & 1) << p) | ((c >> 1) << (32 + p));    // plane-split (scg_common.h)
-        }
+        typename T::Key key = typename T::Key();
+        for (int p = 0; p < len; ++p) T::set_base(key, p, static_cast<uint64_t>(codes[p][choice[p]]));
         f(key);
+        if (plain) return;      // the usual library: A, C, G, T only
         int p = len - 1;
         for (; p >= 0; --p) {
             if (++choice[p] < cnt[p]) break;
@@ -135,6 +174,7 @@ uint32_t capacity_for(int64_t entries, int slots_per_entry = 2) {
     return static_cast<uint32_t>(cap);
 }
 
+// The pair table (build_pair_table): keys in the slots, SCG_EMPTY_KEY where free, as the device probes it.
 struct Builder {
     std::vector<uint64_t>& keys;
     std::vector<int32_t>& vals;
@@ -154,11 +194,28 @@ struct Builder {
     }
 };
 
-void check_len(int32_t len) {
-    if (len > SCG_MAX_BARCODE) {
-        throw Error(SCG_ERR_UNSUPPORTED, "variable regions longer than 32 bp are not supported by this engine (got " + std::to_string(len) + ")");
+// The distinct keys of a pool in the order met, with an exact host-only map from a key to its number in that order: open
+// addressing over the numbers, half full at most, so that no key value has to stand for a free slot.
+template<class T>
+struct KeySet {
+    std::vector<typename T::Key> keys;
+    std::vector<int32_t> slots;
+    explicit KeySet(int64_t total) : slots(capacity_for(total), -1) { keys.reserve(static_cast<size_t>(total)); }
+    // Returns the number of `key`, appending it if absent; *existed tells which.
+    int32_t upsert(const typename T::Key& key, bool* existed) {
+        const uint32_t mask = static_cast<uint32_t>(slots.size()) - 1;
+        for (uint32_t h = T::hash(key) & mask;; h = (h + 1) & mask) {
+            const int32_t e = slots[h];
+            if (e < 0) {
+                slots[h] = static_cast<int32_t>(keys.size());
+                keys.push_back(key);
+                *existed = false;
+                return slots[h];
+            }
+            if (keys[e] == key) { *existed = true; return e; }
+        }
     }
-}
+};
 
 [[noreturn]] void throw_duplicate(int32_t a, int32_t b) {
     // kaori/MismatchTrie.hpp:119-122
@@ -264,16 +321,19 @@ void for_each_group(int n, F fn) {
 }
 
 // Lays the concrete entries (key, value) out as a segment index (scg_common.h: ScgIndex).
-void finish_index(HostIndex& X, const std::vector<uint64_t>& keys, const std::vector<int32_t>& vals, int32_t len, int max_mm) {
+template<class T>
+void finish_index(HostIndex& X, const std::vector<typename T::Key>& keys, const std::vector<int32_t>& vals, int32_t len, int max_mm) {
+    constexpr int NW = T::WORDS, NEXT = T::VALUE + 1;
     const size_t n = keys.size();
+    X.wide = T::CLS;
     X.len = len;
     X.n_entries = static_cast<int32_t>(n);
-    // position groups (see ScgIndex): masks over `parts` equal slices of the barcode
+    // position groups (see ScgIndex): one or two of `parts` equal slices of the barcode, each a range [a, b) of positions
+    // packed as a | b << 16, the second 32 bits up (scg_big_group)
     auto slice = [&](int part, int parts) -> uint64_t {
-        int a = static_cast<int>(static_cast<int64_t>(part) * len / parts);
-        int b = static_cast<int>(static_cast<int64_t>(part + 1) * len / parts);
-        uint64_t m32 = (b - a >= 32) ? 0xFFFFFFFFull : (((1ull << (b - a)) - 1ull) << a);
-        return m32 | (m32 << 32);
+        const uint64_t a = static_cast<uint64_t>(static_cast<int64_t>(part) * len / parts);
+        const uint64_t b = static_cast<uint64_t>(static_cast<int64_t>(part + 1) * len / parts);
+        return a | (b << 16);
     };
     std::vector<uint64_t> groups;
     if (max_mm == 0) {
@@ -285,7 +345,7 @@ void finish_index(HostIndex& X, const std::vector<uint64_t>& keys, const std::ve
         X.nwalk[0] = 1; X.nwalk[1] = X.nwalk[2] = X.nwalk[3] = 2;
     } else if (max_mm == 2) {
         static const int pairs[6][2] = {{0, 1}, {2, 3}, {0, 2}, {1, 3}, {0, 3}, {1, 2}};
-        for (auto& pr : pairs) groups.push_back(slice(pr[0], 4) | slice(pr[1], 4));
+        for (auto& pr : pairs) groups.push_back(slice(pr[0], 4) | (slice(pr[1], 4) << 32));
         X.nwalk[0] = 1; X.nwalk[1] = 2; X.nwalk[2] = X.nwalk[3] = 6;
     } else if (max_mm == 3) {
         for (int q = 0; q < 4; ++q) groups.push_back(slice(q, 4));
@@ -294,14 +354,13 @@ void finish_index(HostIndex& X, const std::vector<uint64_t>& keys, const std::ve
     const int nseg = static_cast<int>(groups.size());
     X.nseg = nseg;
     const int ncopies = nseg > 0 ? nseg : 1;
-    X.nodes.resize(static_cast<size_t>(ncopies) * n * 4);
+    X.nodes.resize(static_cast<size_t>(ncopies) * n * NW);      // (zeros: the padding words stay so)
     for (int c = 0; c < ncopies; ++c) {
-        uint32_t* node = X.nodes.data() + static_cast<size_t>(c) * n * 4;
+        uint32_t* node = X.nodes.data() + static_cast<size_t>(c) * n * NW;
         for (size_t e = 0; e < n; ++e) {
-            node[4 * e] = static_cast<uint32_t>(keys[e]);
-            node[4 * e + 1] = static_cast<uint32_t>(keys[e] >> 32);
-            node[4 * e + 2] = static_cast<uint32_t>(vals[e]);
-            node[4 * e + 3] = 0xFFFFFFFFu;          // chain end until linked below
+            T::put_key(node + NW * e, keys[e]);
+            node[NW * e + T::VALUE] = static_cast<uint32_t>(vals[e]);
+            node[NW * e + NEXT] = 0xFFFFFFFFu;      // chain end until linked below
         }
     }
     if (nseg == 0) return;
@@ -313,227 +372,23 @@ void finish_index(HostIndex& X, const std::vector<uint64_t>& keys, const std::ve
     uint32_t cap = 16;
     while (cap < n * table_factor(n)) cap <<= 1;
     X.slot_mask = cap - 1;
-    X.tables.resize(static_cast<size_t>(nseg) * cap * 4);
-    for (int sgm = 0; sgm < nseg; ++sgm) X.segmask[sgm] = groups[sgm];
-    for_each_group(nseg, [&](int sgm) {
-        const uint64_t mask = groups[sgm];
-        const uint32_t slot_mask = X.slot_mask;
-        uint32_t* node = X.nodes.data() + static_cast<size_t>(sgm) * n * 4;
-        uint32_t* table = X.tables.data() + static_cast<size_t>(sgm) * cap * 4;
-        std::vector<int32_t> placed(cap, -1);
-        for (size_t i = n; i-- > 0;) {
-            const uint64_t sk = keys[i] & mask;
-            uint32_t pos = scg_hash64(sk) & slot_mask;
-            for (;;) {
-                const int32_t e = placed[pos];
-                if (e < 0) { placed[pos] = static_cast<int32_t>(i); break; }
-                if ((keys[e] & mask) == sk) {
-                    node[4 * i + 3] = static_cast<uint32_t>(e);
-                    placed[pos] = static_cast<int32_t>(i);
-                    break;
-                }
-                pos = (pos + 1) & slot_mask;
-            }
-        }
-        for (uint32_t pos = 0; pos < cap; ++pos) {
-            const int32_t e = placed[pos];
-            if (e < 0) {
-                table[4 * pos] = table[4 * pos + 1] = table[4 * pos + 2] = 0;
-                table[4 * pos + 3] = SCG_SLOT_EMPTY;
-            } else {
-                for (int w = 0; w < 4; ++w) table[4 * pos + w] = node[4 * static_cast<size_t>(e) + w];
-            }
-        }
-    });
-}
-
-} // namespace
-
-HostIndex build_index(const char* const* pool, int32_t n, int32_t len, int max_mm) {
-    check_len(len);
-    int64_t total = count_expansions(pool, n, len);
-    std::vector<uint64_t> hk;
-    std::vector<int32_t> hv;
-    Builder B(hk, hv, capacity_for(total));     // host-only exact map, for duplicate detection
-    int32_t sentinel = -1;                      // owner of the one key equal to SCG_EMPTY_KEY (32 x G)
-    std::vector<uint64_t> keys;
-    std::vector<int32_t> vals;
-    keys.reserve(total);
-    vals.reserve(total);
-    for (int32_t i = 0; i < n; ++i) {
-        for_each_expansion(pool[i], len, [&](uint64_t key) {
-            if (key == SCG_EMPTY_KEY) {
-                if (sentinel >= 0) throw_duplicate(sentinel, i);
-                sentinel = i;
-            } else {
-                bool existed;
-                uint32_t slot = B.upsert(key, i, &existed);
-                if (existed) throw_duplicate(hv[slot], i);
-            }
-            keys.push_back(key);
-            vals.push_back(i);
-        });
-    }
-    HostIndex X;
-    finish_index(X, keys, vals, len, max_mm);
-    return X;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Wide keys (33..64 bases, or several regions concatenated: N = 1 word of 64 bits per plane) and big keys (65..256
-// bases: N = SCG_BIG_WORDS): the same index.  A node / slot is {lo words}{hi words}{value, next}, padded to whole uint4:
-// 8 and 20 32-bit words.
-// ---------------------------------------------------------------------------------------------
-namespace {
-
-template<int N>
-struct KeyN {
-    uint64_t lo[N], hi[N];
-    bool operator==(const KeyN& o) const {
-        for (int k = 0; k < N; ++k) if (lo[k] != o.lo[k] || hi[k] != o.hi[k]) return false;
-        return true;
-    }
-};
-template<int N>
-struct KeyNHash {
-    size_t operator()(const KeyN<N>& k) const {
-        size_t h = 0;
-        for (int w = 0; w < N; ++w) {
-            h = h * 0x9E3779B97F4A7C15ull + ((static_cast<size_t>(scg_hash64(k.lo[w])) << 32) ^ scg_hash64(k.hi[w]) ^ (k.lo[w] * 0x9E3779B97F4A7C15ull));
-        }
-        return h;
-    }
-};
-template<int N> constexpr int node_words() { return N == 1 ? 8 : 20; }
-template<int N> uint32_t group_hash(const KeyN<N>& k);
-template<> uint32_t group_hash<1>(const KeyN<1>& k) { return scg_hash128(k.lo[0], k.hi[0]); }
-template<> uint32_t group_hash<SCG_BIG_WORDS>(const KeyN<SCG_BIG_WORDS>& k) { return scg_hash_big(k.lo, k.hi); }
-
-template<int N, class F>
-void for_each_expansion_n(const char* s, int len, F f) {
-    constexpr int MAXLEN = 64 * N;
-    int cnt[MAXLEN], codes[MAXLEN][4], choice[MAXLEN];
-    for (int p = 0; p < len; ++p) {
-        cnt[p] = iupac_codes(s[p], codes[p]);
-        choice[p] = 0;
-    }
-    for (;;) {
-        KeyN<N> key;
-        std::memset(&key, 0, sizeof(key));
-        for (int p = 0; p < len; ++p) {
-            uint64_t c = static_cast<uint64_t>(codes[p][choice[p]]);
-            key.lo[p >> 6] |= (c & 1) << (p & 63);
-            key.hi[p >> 6] |= (c >> 1) << (p & 63);
-        }
-        f(key);
-        int p = len - 1;
-        for (; p >= 0; --p) {
-            if (++choice[p] < cnt[p]) break;
-            choice[p] = 0;
-        }
-        if (p < 0) break;
-    }
-}
-
-template<int N>
-void put_node(uint32_t* node, const KeyN<N>& k, uint32_t val, uint32_t next) {
-    for (int w = 0; w < N; ++w) {
-        node[2 * w] = static_cast<uint32_t>(k.lo[w]); node[2 * w + 1] = static_cast<uint32_t>(k.lo[w] >> 32);
-        node[2 * N + 2 * w] = static_cast<uint32_t>(k.hi[w]); node[2 * N + 2 * w + 1] = static_cast<uint32_t>(k.hi[w] >> 32);
-    }
-    node[4 * N] = val; node[4 * N + 1] = next;
-    for (int w = 4 * N + 2; w < node_words<N>(); ++w) node[w] = 0;
-}
-
-template<int N>
-void check_len_n(int len) {
-    if (len > 64 * N) {
-        throw Error(SCG_ERR_UNSUPPORTED, "variable regions longer than " + std::to_string(64 * N) + " bp in total are not supported by this engine (got " +
-                                         std::to_string(len) + ")");
-    }
-}
-
-// A group of key positions: up to two ranges [a, b).
-struct Group { int a0, b0, a1, b1; };
-
-template<int N>
-KeyN<N> masked(const KeyN<N>& k, const uint64_t mask[N]) {
-    KeyN<N> r;
-    for (int w = 0; w < N; ++w) { r.lo[w] = k.lo[w] & mask[w]; r.hi[w] = k.hi[w] & mask[w]; }
-    return r;
-}
-
-// Tables and node copies of a wide / big index over concrete keys with their values.
-template<int N>
-void finish_index_n(HostIndex& X, const std::vector<KeyN<N> >& keys, const std::vector<int32_t>& vals, int32_t len, int max_mm) {
-    constexpr int NW = node_words<N>();
-    X.wide = N == 1 ? 1 : 2;
-    X.len = len;
-    const size_t cnt = keys.size();
-    X.n_entries = static_cast<int32_t>(cnt);
-    auto slice = [&](int part, int parts, int& a, int& b) {
-        a = static_cast<int>(static_cast<int64_t>(part) * len / parts);
-        b = static_cast<int>(static_cast<int64_t>(part + 1) * len / parts);
-    };
-    std::vector<Group> groups;              // same position groups as finish_index
-    auto one = [&](int part, int parts) { Group g{0, 0, 0, 0}; slice(part, parts, g.a0, g.b0); groups.push_back(g); };
-    if (max_mm == 0) {
-        one(0, 1);
-        X.nwalk[0] = X.nwalk[1] = X.nwalk[2] = X.nwalk[3] = 1;
-    } else if (max_mm == 1) {
-        one(0, 2);
-        one(1, 2);
-        X.nwalk[0] = 1; X.nwalk[1] = X.nwalk[2] = X.nwalk[3] = 2;
-    } else if (max_mm == 2) {
-        static const int pairs[6][2] = {{0, 1}, {2, 3}, {0, 2}, {1, 3}, {0, 3}, {1, 2}};
-        for (auto& pr : pairs) {
-            Group g;
-            slice(pr[0], 4, g.a0, g.b0);
-            slice(pr[1], 4, g.a1, g.b1);
-            groups.push_back(g);
-        }
-        X.nwalk[0] = 1; X.nwalk[1] = 2; X.nwalk[2] = X.nwalk[3] = 6;
-    } else if (max_mm == 3) {
-        for (int q = 0; q < 4; ++q) one(q, 4);
-        X.nwalk[0] = 1; X.nwalk[1] = 2; X.nwalk[2] = 3; X.nwalk[3] = 4;
-    }
-    const int nseg = static_cast<int>(groups.size());
-    X.nseg = nseg;
-    const int ncopies = nseg > 0 ? nseg : 1;
-    X.nodes.resize(static_cast<size_t>(ncopies) * cnt * NW);
-    for (int c = 0; c < ncopies; ++c) {
-        uint32_t* node = X.nodes.data() + static_cast<size_t>(c) * cnt * NW;
-        for (size_t e = 0; e < cnt; ++e) put_node<N>(node + NW * e, keys[e], static_cast<uint32_t>(vals[e]), 0xFFFFFFFFu);
-    }
-    if (nseg == 0) return;
-    uint32_t cap = 16;
-    while (cap < cnt * table_factor(cnt)) cap <<= 1;
-    X.slot_mask = cap - 1;
     X.tables.resize(static_cast<size_t>(nseg) * cap * NW);
-    std::vector<std::array<uint64_t, N> > masks(nseg);
-    for (int sgm = 0; sgm < nseg; ++sgm) {
-        const Group& g = groups[sgm];
-        const uint64_t ranges = static_cast<uint64_t>(g.a0) | (static_cast<uint64_t>(g.b0) << 16) | (static_cast<uint64_t>(g.a1) << 32) | (static_cast<uint64_t>(g.b1) << 48);
-        uint64_t m[SCG_BIG_WORDS];
-        scg_big_group(ranges, m);
-        for (int w = 0; w < N; ++w) masks[sgm][w] = m[w];
-        // wide: the 64-bit position mask itself; big: the ranges (ScgIndex::segmask)
-        X.segmask[sgm] = N == 1 ? m[0] : ranges;
-    }
-    for_each_group(nseg, [&](int sgm) {             // as finish_index
-        const uint64_t* mask = masks[sgm].data();
+    uint64_t masks[SCG_MAX_SEGMENTS][SCG_BIG_WORDS];
+    for (int sgm = 0; sgm < nseg; ++sgm) X.segmask[sgm] = T::group(groups[sgm], masks[sgm]);
+    for_each_group(nseg, [&](int sgm) {
+        const uint64_t* mask = masks[sgm];
         const uint32_t slot_mask = X.slot_mask;
-        uint32_t* node = X.nodes.data() + static_cast<size_t>(sgm) * cnt * NW;
+        uint32_t* node = X.nodes.data() + static_cast<size_t>(sgm) * n * NW;
         uint32_t* table = X.tables.data() + static_cast<size_t>(sgm) * cap * NW;
         std::vector<int32_t> placed(cap, -1);
-        for (size_t i = cnt; i-- > 0;) {
-            const KeyN<N> sk = masked<N>(keys[i], mask);
-            uint32_t pos = group_hash<N>(sk) & slot_mask;
+        for (size_t i = n; i-- > 0;) {
+            const typename T::Key sk = T::masked(keys[i], mask);
+            uint32_t pos = T::hash(sk) & slot_mask;
             for (;;) {
                 const int32_t e = placed[pos];
                 if (e < 0) { placed[pos] = static_cast<int32_t>(i); break; }
-                if (masked<N>(keys[e], mask) == sk) {
-                    node[NW * i + 4 * N + 1] = static_cast<uint32_t>(e);
+                if (T::masked(keys[e], mask) == sk) {
+                    node[NW * i + NEXT] = static_cast<uint32_t>(e);
                     placed[pos] = static_cast<int32_t>(i);
                     break;
                 }
@@ -542,112 +397,60 @@ void finish_index_n(HostIndex& X, const std::vector<KeyN<N> >& keys, const std::
         }
         for (uint32_t pos = 0; pos < cap; ++pos) {
             const int32_t e = placed[pos];
-            if (e < 0) {
-                for (int w = 0; w < NW; ++w) table[NW * pos + w] = 0;
-                table[NW * pos + 4 * N + 1] = SCG_SLOT_EMPTY;
-            } else {
-                for (int w = 0; w < NW; ++w) table[NW * pos + w] = node[NW * static_cast<size_t>(e) + w];
-            }
+            uint32_t* slot = table + static_cast<size_t>(NW) * pos;
+            if (e < 0) slot[NEXT] = SCG_SLOT_EMPTY;      // (the other words are zero)
+            else for (int w = 0; w < NW; ++w) slot[w] = node[NW * static_cast<size_t>(e) + w];
         }
     });
 }
 
-template<int N>
-HostIndex build_index_n(const char* const* pool, int32_t n, int32_t len, int max_mm) {
-    check_len_n<N>(len);
-    count_expansions(pool, n, len);
-    std::unordered_map<KeyN<N>, int32_t, KeyNHash<N> > owner;
-    std::vector<KeyN<N> > keys;
+// The index of a pool in key class T.  Without `expansions`, value = barcode index and a sequence met twice is an error;
+// with it, value = uid, the sequence's number among the distinct ones in the order met, and expansions[i] lists barcode i's.
+template<class T>
+HostIndex build(const char* const* pool, int32_t n, int32_t len, int max_mm, std::vector<std::vector<int32_t> >* expansions,
+                std::vector<uint64_t>* uid_keys) {
+    if (len > T::MAXLEN) {
+        throw Error(SCG_ERR_UNSUPPORTED, "variable regions longer than " + std::to_string(T::MAXLEN) + (T::CLS ? " bp in total" : " bp") +
+                                         " are not supported by this engine (got " + std::to_string(len) + ")");
+    }
+    const int64_t total = count_expansions(pool, n, len);
+    KeySet<T> seen(total);
     std::vector<int32_t> vals;
+    vals.reserve(static_cast<size_t>(total));
+    if (expansions) expansions->assign(n, std::vector<int32_t>());
     for (int32_t i = 0; i < n; ++i) {
-        for_each_expansion_n<N>(pool[i], len, [&](const KeyN<N>& key) {
-            auto ins = owner.emplace(key, i);
-            if (!ins.second) throw_duplicate(ins.first->second, i);
-            keys.push_back(key);
-            vals.push_back(i);
+        for_each_expansion<T>(pool[i], len, [&](const typename T::Key& key) {
+            bool existed;
+            const int32_t e = seen.upsert(key, &existed);
+            if (expansions) (*expansions)[i].push_back(e);
+            else if (existed) throw_duplicate(vals[e], i);
+            if (!existed) vals.push_back(expansions ? e : i);
         });
     }
     HostIndex X;
-    finish_index_n<N>(X, keys, vals, len, max_mm);
+    finish_index<T>(X, seen.keys, vals, len, max_mm);
+    if constexpr (T::CLS == 0) {
+        if (uid_keys) *uid_keys = std::move(seen.keys);
+    }
     return X;
 }
 
-template<int N>
-HostIndex build_uid_index_n(const char* const* pool, int32_t n, int32_t len, int max_mm,
-                            std::vector<std::vector<int32_t> >& expansions, size_t& n_uid) {
-    check_len_n<N>(len);
-    count_expansions(pool, n, len);
-    std::unordered_map<KeyN<N>, int32_t, KeyNHash<N> > uid_of;
-    std::vector<KeyN<N> > keys;
-    expansions.assign(n, std::vector<int32_t>());
-    for (int32_t i = 0; i < n; ++i) {
-        for_each_expansion_n<N>(pool[i], len, [&](const KeyN<N>& key) {
-            auto ins = uid_of.emplace(key, static_cast<int32_t>(keys.size()));
-            if (ins.second) keys.push_back(key);
-            expansions[i].push_back(ins.first->second);
-        });
-    }
-    std::vector<int32_t> vals(keys.size());
-    for (size_t u = 0; u < keys.size(); ++u) vals[u] = static_cast<int32_t>(u);
-    n_uid = keys.size();
-    HostIndex X;
-    finish_index_n<N>(X, keys, vals, len, max_mm);
-    return X;
+HostIndex build_class(int cls, const char* const* pool, int32_t n, int32_t len, int max_mm, std::vector<std::vector<int32_t> >* expansions,
+                      std::vector<uint64_t>* uid_keys) {
+    if (cls == 0) return build<Narrow>(pool, n, len, max_mm, expansions, uid_keys);
+    return cls == 1 ? build<Planes<1> >(pool, n, len, max_mm, expansions, uid_keys) : build<Planes<SCG_BIG_WORDS> >(pool, n, len, max_mm, expansions, uid_keys);
 }
 
 } // namespace
 
-HostIndex build_index_wide(const char* const* pool, int32_t n, int32_t len, int max_mm) {
-    return len > SCG_MAX_WIDE_BARCODE ? build_index_n<SCG_BIG_WORDS>(pool, n, len, max_mm) : build_index_n<1>(pool, n, len, max_mm);
+HostIndex build_index(const char* const* pool, int32_t n, int32_t len, int max_mm, int cls) {
+    return build_class(cls, pool, n, len, max_mm, nullptr, nullptr);
 }
 
-// value = uid of the concrete sequence, wide keys (build_uid_index for pools of 33..64 bases, or paired with one).
-HostIndex build_uid_index_wide(const char* const* pool, int32_t n, int32_t len, int max_mm,
-                               std::vector<std::vector<int32_t> >& expansions, size_t& n_uid) {
-    return len > SCG_MAX_WIDE_BARCODE ? build_uid_index_n<SCG_BIG_WORDS>(pool, n, len, max_mm, expansions, n_uid)
-                                      : build_uid_index_n<1>(pool, n, len, max_mm, expansions, n_uid);
-}
-
-HostIndex build_index_big(const char* const* pool, int32_t n, int32_t len, int max_mm) { return build_index_n<SCG_BIG_WORDS>(pool, n, len, max_mm); }
-HostIndex build_uid_index_big(const char* const* pool, int32_t n, int32_t len, int max_mm,
-                              std::vector<std::vector<int32_t> >& expansions, size_t& n_uid) {
-    return build_uid_index_n<SCG_BIG_WORDS>(pool, n, len, max_mm, expansions, n_uid);
-}
-
-HostIndex build_uid_index(const char* const* pool, int32_t n, int32_t len, int max_mm,
-                          std::vector<std::vector<int32_t> >& expansions,
-                          std::vector<uint64_t>& uid_keys) {
-    check_len(len);
-    int64_t total = count_expansions(pool, n, len);
-    std::vector<uint64_t> hk;
-    std::vector<int32_t> hv;
-    Builder B(hk, hv, capacity_for(total));
-    int32_t sentinel = -1;
-    expansions.assign(n, std::vector<int32_t>());
+HostIndex build_uid_index(const char* const* pool, int32_t n, int32_t len, int max_mm, int cls,
+                          std::vector<std::vector<int32_t> >& expansions, std::vector<uint64_t>& uid_keys) {
     uid_keys.clear();
-    for (int32_t i = 0; i < n; ++i) {
-        for_each_expansion(pool[i], len, [&](uint64_t key) {
-            int32_t uid;
-            if (key == SCG_EMPTY_KEY) {
-                if (sentinel < 0) {
-                    sentinel = static_cast<int32_t>(uid_keys.size());
-                    uid_keys.push_back(key);
-                }
-                uid = sentinel;
-            } else {
-                bool existed;
-                uint32_t slot = B.upsert(key, static_cast<int32_t>(uid_keys.size()), &existed);
-                if (!existed) uid_keys.push_back(key);
-                uid = hv[slot];
-            }
-            expansions[i].push_back(uid);
-        });
-    }
-    std::vector<int32_t> vals(uid_keys.size());
-    for (size_t u = 0; u < uid_keys.size(); ++u) vals[u] = static_cast<int32_t>(u);
-    HostIndex X;
-    finish_index(X, uid_keys, vals, len, max_mm);
-    return X;
+    return build_class(cls, pool, n, len, max_mm, &expansions, &uid_keys);
 }
 
 HostPairTable build_pair_table(const std::vector<std::vector<int32_t> >& exp1, const std::vector<uint64_t>& uid_keys1,

@@ -7,19 +7,7 @@
 #include "scg_internal.hpp"
 
 namespace scgapi {
-// Key width classes: 0 = up to 32 bases (2 x 32-bit planes), 1 = up to 64, 2 = up to 256 ("big").  Pools that meet in one
-// kernel (both regions of a combination, both mates of a pair) are built in the widest class among them.
-int key_class(int len) { return len > SCG_MAX_WIDE_BARCODE ? 2 : (len > SCG_MAX_BARCODE ? 1 : 0); }
-
-scg::HostIndex build_index_class(int cls, const char* const* pool, int32_t n, int32_t len, int max_mm) {
-    if (cls == 2) return scg::build_index_big(pool, n, len, max_mm);
-    return cls == 1 ? scg::build_index_wide(pool, n, len, max_mm) : scg::build_index(pool, n, len, max_mm);
-}
-scg::HostIndex build_uid_index_class(int cls, const char* const* pool, int32_t n, int32_t len, int max_mm,
-                                     std::vector<std::vector<int32_t> >& expansions, size_t& n_uid) {
-    if (cls == 2) return scg::build_uid_index_big(pool, n, len, max_mm, expansions, n_uid);
-    return scg::build_uid_index_wide(pool, n, len, max_mm, expansions, n_uid);
-}
+using scg::key_class;
 
 // Big keys have the byte-wise general kernels only, whatever scg::staged_takes says of the batch.
 bool general_only(const scg_plan* P) {
@@ -76,21 +64,17 @@ void check_region_length(const ScgTemplate& t, int r, int plen) {
 }
 
 // The uid indexes of two pools whose sequences meet as pairs (both mates, or both regions of include.invalid=TRUE), into
-// P->htab[0..1]: class 0, or wide / big for both when either pool has more than 32 bases.
+// P->htab[0..1], both in the wider key class of the two.
 struct UidIndexes {
     std::vector<std::vector<int32_t> > exp[2];   // barcode -> the uids of its sequences
     std::vector<uint64_t> keys[2];               // class 0: uid -> key, for the pair table
     size_t n_uid[2] = {0, 0};
 
     UidIndexes(scg_plan* P, const char* const* pool0, int32_t n0, int len0, int mm0, const char* const* pool1, int32_t n1, int len1, int mm1) {
-        if (const int cls = std::max(key_class(len0), key_class(len1))) {
-            P->htab[0] = build_uid_index_class(cls, pool0, n0, len0, mm0, exp[0], n_uid[0]);
-            P->htab[1] = build_uid_index_class(cls, pool1, n1, len1, mm1, exp[1], n_uid[1]);
-        } else {
-            P->htab[0] = scg::build_uid_index(pool0, n0, len0, mm0, exp[0], keys[0]);
-            P->htab[1] = scg::build_uid_index(pool1, n1, len1, mm1, exp[1], keys[1]);
-            n_uid[0] = keys[0].size(); n_uid[1] = keys[1].size();
-        }
+        const int cls = std::max(key_class(len0), key_class(len1));
+        P->htab[0] = scg::build_uid_index(pool0, n0, len0, mm0, cls, exp[0], keys[0]);
+        P->htab[1] = scg::build_uid_index(pool1, n1, len1, mm1, cls, exp[1], keys[1]);
+        for (int side = 0; side < 2; ++side) n_uid[side] = static_cast<size_t>(P->htab[side].n_entries);
     }
     // uid -> index of the first barcode that contains the sequence
     std::vector<int32_t> first(int side) const {
@@ -119,8 +103,8 @@ std::unique_ptr<scg_plan> compile_single(const char* constant, int strand, const
     P->ht1 = scg::parse_template(constant, strand);            // src/count_single_barcodes.cpp:37-47, ScanTemplate.hpp:53-95
     check_single_match(P->ht1, plen);
     if (mismatches < 0) throw Error(SCG_ERR_INVALID, "negative number of mismatches");
-    // BarcodeSearch.hpp:23-60; barcodes of 33..64 bases take the wide (2 x 64-bit plane) index and kernels
-    P->htab[0] = plen > SCG_MAX_BARCODE ? scg::build_index_wide(pool, n_pool, plen, mismatches) : scg::build_index(pool, n_pool, plen, mismatches);
+    // BarcodeSearch.hpp:23-60; barcodes of 33..64 bases take the wide (2 x 64-bit plane) index and kernels, longer ones the big
+    P->htab[0] = scg::build_index(pool, n_pool, plen, mismatches, key_class(plen));
     P->scan1 = scg::build_scan(P->ht1.t, mismatches);
     P->n_pool[0] = n_pool;
     P->n_counters = n_pool;
@@ -175,7 +159,7 @@ std::unique_ptr<scg_plan> compile_dual_single_end(const char* constant, int stra
         for (int r = 0; r < n_regions; ++r) combined[c].append(pools[r][c], plen[r]);
         ptrs[c] = combined[c].c_str();
     }
-    P->htab[0] = scg::build_index_wide(ptrs.data(), n_choices, total, mismatches);     // duplicates => error (:111-113)
+    P->htab[0] = scg::build_index(ptrs.data(), n_choices, total, mismatches, std::max(1, key_class(total)));     // duplicates => error (:111-113)
     P->scan1 = scg::build_scan(t, mismatches);
     P->n_pool[0] = n_choices;
     P->n_counters = n_choices;
@@ -202,8 +186,8 @@ std::unique_ptr<scg_plan> compile_combo(const char* constant, int strand,
     // pools of 33..64 bases take the wide (2 x 64-bit plane) index and kernels, longer ones the big one; both pools then, one
     // key width per kernel
     const int cls = std::max(key_class(len0), key_class(len1));
-    P->htab[0] = build_index_class(cls, pool0, n0, len0, mismatches);
-    P->htab[1] = build_index_class(cls, pool1, n1, len1, mismatches);
+    P->htab[0] = scg::build_index(pool0, n0, len0, mismatches, cls);
+    P->htab[1] = scg::build_index(pool1, n1, len1, mismatches, cls);
     P->scan1 = scg::build_scan(P->ht1.t, mismatches);
     P->n_pool[0] = n0; P->n_pool[1] = n1;
     int64_t cells = static_cast<int64_t>(n0) * static_cast<int64_t>(n1);
@@ -283,8 +267,8 @@ std::unique_ptr<scg_plan> compile_paired_combo(const char* constant1, int revers
     check_single_match(P->ht2, len2);
     if (mismatches1 < 0 || mismatches2 < 0) throw Error(SCG_ERR_INVALID, "negative number of mismatches");
     const int cls = std::max(key_class(len1), key_class(len2));
-    P->htab[0] = build_index_class(cls, pool1, n1, len1, mismatches1);     // values = pool indices; duplicates => error
-    P->htab[1] = build_index_class(cls, pool2, n2, len2, mismatches2);
+    P->htab[0] = scg::build_index(pool1, n1, len1, mismatches1, cls);     // values = pool indices; duplicates => error
+    P->htab[1] = scg::build_index(pool2, n2, len2, mismatches2, cls);
     P->scan1 = scg::build_scan(P->ht1.t, mismatches1);
     P->scan2 = scg::build_scan(P->ht2.t, mismatches2);
     int64_t cells = static_cast<int64_t>(n1) * static_cast<int64_t>(n2);
