@@ -469,6 +469,28 @@ int scg_count_batch_paired(scg_plan* plan,
                            const char* d_seqs2, const uint32_t* d_offsets2, int32_t fixed_len2,
                            int32_t max_len, int64_t n_pairs, void* stream, char* err, size_t errcap);
 
+/* What each read of a batch matched: the State of kaori::SimpleSingleMatch (inst/include/kaori/SimpleSingleMatch.hpp:103-140)
+ * that search_first / search_best (:200-306; the plan's use_first picks one) leave for the read, in five caller-owned device
+ * arrays of n_reads elements:
+ *   d_index_out                0-based barcode index                                   (required)
+ *   d_position_out             start of the template's window in the read, as given -- also for a reverse-strand match
+ *   d_mismatches_out           mismatches of the whole window, constant and variable bases
+ *   d_variable_mismatches_out  those inside the variable region
+ *   d_reverse_out              1 when the match is on the reverse strand, else 0
+ * A read without a match -- none within the budget, a tie between two barcodes in best mode, a read shorter than the
+ * template, an empty read -- has -1 in all five (the reference returns false and leaves its State stale).  Any of the last
+ * four may be NULL and is then not written.  The batch arguments are those of scg_count_batch, checked the same way.
+ * Plans of scg_plan_single only: every other kind is SCG_ERR_INVALID, and a plan whose mismatch budget exceeds 127 is
+ * SCG_ERR_UNSUPPORTED (the int8 outputs could not hold it); both before any device work.
+ * Asynchronous on `stream`.  The plan's counters and read total are not touched: counting and assigning may be interleaved
+ * freely, and scg_plan_read gives what it would have given without the assign calls.  A wrong max_len hint is reported
+ * by the next scg_plan_read, as for scg_count_batch.  n_reads == 0 launches nothing. */
+int scg_assign_batch(scg_plan* plan, const char* d_seqs, const uint32_t* d_offsets, int32_t fixed_len,
+                     int32_t max_len, int64_t n_reads,
+                     int32_t* d_index_out, int32_t* d_position_out, int8_t* d_mismatches_out,
+                     int8_t* d_variable_mismatches_out, int8_t* d_reverse_out,
+                     void* stream, char* err, size_t errcap);
+
 /* Synchronise `stream` and copy the counters (num_counters int32) and the number of reads seen
  * so far to the host.  Either output may be NULL. */
 int scg_plan_read(scg_plan* plan, int32_t* counts_out, int64_t* total_out, void* stream,

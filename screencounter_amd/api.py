@@ -466,6 +466,29 @@ def count_combo_barcodes_paired(path1: str, constant1: str, reverse1: bool, mism
     return idx.astype(np.int32), freq.astype(np.int32), int(total.value), int(b1.value), int(b2.value)
 
 
+def assign_single_barcodes(path: str, template: str, strand: int, pool: Sequence[str], mismatches: int = 0, use_first: bool = True,
+                           batch_reads: int = 1 << 22, device: int = -1):
+    """What every read of a FASTQ file matched: kaori::SimpleSingleMatch::State per read (SimpleSingleMatch.hpp:103-140) as
+    an engine.Assignment of five numpy arrays of the file's read count -- index and position int32, mismatches,
+    variable_mismatches and reverse int8, -1 everywhere for a read without a match.  The file is parsed on the host
+    (parse_fastq) and assigned in batches of batch_reads reads through Plan.assign."""
+    from .engine import ASSIGN_FIELDS, Assignment, Plan, upload_reads
+    if batch_reads <= 0:
+        raise ValueError("batch_reads must be positive")
+    seqs, offs = parse_fastq(path)
+    n = len(offs) - 1
+    parts = [[] for _ in ASSIGN_FIELDS]
+    with Plan.single(template, strand, pool, mismatches, use_first, device) as plan:
+        for a in range(0, n, batch_reads):
+            b = min(n, a + batch_reads)
+            lo, hi = int(offs[a]), int(offs[b])
+            s, o = upload_reads((seqs[lo:hi], offs[a:b + 1] - offs[a]), "cuda" if device < 0 else f"cuda:{device}")
+            for part, t in zip(parts, plan.assign(s, o)):
+                part.append(t.cpu().numpy())
+    return Assignment(*(np.concatenate(p) if p else np.zeros(0, dtype=np.int32 if f in ("index", "position") else np.int8)
+                        for p, f in zip(parts, ASSIGN_FIELDS)))
+
+
 def match_barcodes(sequences: Sequence[str], choices: Sequence[str], substitutions: int = 0, reverse: bool = False):
     """src/match_barcodes.cpp:6-37 -> (index int32[n] 0-based with -1 for NA, mismatches int32[n] with -1 for NA)."""
     L = _lib.load()

@@ -317,6 +317,28 @@ int scg_count_batch_paired(scg_plan* plan, const char* d_seqs1, const uint32_t* 
     });
 }
 
+int scg_assign_batch(scg_plan* plan, const char* d_seqs, const uint32_t* d_offsets, int32_t fixed_len, int32_t max_len, int64_t n_reads,
+                     int32_t* d_index_out, int32_t* d_position_out, int8_t* d_mismatches_out, int8_t* d_variable_mismatches_out,
+                     int8_t* d_reverse_out, void* stream, char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (!plan) throw Error(SCG_ERR_INVALID, "null plan");
+        if (n_reads > 0 && !d_index_out) throw Error(SCG_ERR_INVALID, "null argument");
+        if (plan->kind != scg_plan::SINGLE || !plan->simple_match) {
+            throw Error(SCG_ERR_INVALID, "scg_assign_batch needs a single-barcode plan (scg_plan_single)");
+        }
+        check_reads_args(d_seqs, d_offsets, fixed_len, n_reads);
+        if (plan->max_mm1 > INT8_MAX) {
+            throw Error(SCG_ERR_UNSUPPORTED, "scg_assign_batch reports mismatches as int8: a budget of " + std::to_string(plan->max_mm1) + " exceeds 127");
+        }
+        if (n_reads == 0) return;
+        DeviceGuard g(plan->device);
+        ScgAssignOut out;
+        out.index = d_index_out; out.position = d_position_out; out.mismatches = d_mismatches_out;
+        out.variable_mismatches = d_variable_mismatches_out; out.reverse = d_reverse_out;
+        launch_batch_assign(plan, make_reads(d_seqs, d_offsets, fixed_len, max_len), n_reads, out, static_cast<hipStream_t>(stream));
+    });
+}
+
 int scg_plan_read(scg_plan* plan, int32_t* counts_out, int64_t* total_out, void* stream, char* err, size_t errcap) {
     return guarded(err, errcap, [&] {
         if (!plan) throw Error(SCG_ERR_INVALID, "null plan");

@@ -187,6 +187,17 @@ struct ScgSingleParams {
     int32_t fwd, rev;
 };
 
+// Where the assign kernels write the match state of read r (kaori::SimpleSingleMatch::State, SimpleSingleMatch.hpp:103-140):
+// element r of each array, -1 in all of them when the read has no match.  `index` is always there; the others may be
+// nullptr (not asked for).
+struct ScgAssignOut {
+    int32_t* index;
+    int32_t* position;
+    int8_t* mismatches;
+    int8_t* variable_mismatches;
+    int8_t* reverse;
+};
+
 struct ScgComboParams {
     ScgScan scan;
     const ScgTemplate* tmpl;

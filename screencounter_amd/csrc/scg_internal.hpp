@@ -272,6 +272,7 @@ struct scg_plan {
     int max_mm1 = 0, max_mm2 = 0;
     bool rev1 = false, rev2 = false, randomized = false, use_first = true;
     int diagnostics = 0;         // 0 none, 1 include.invalid=TRUE, 2 paired combinations (ScgDualParams::diagnostics)
+    bool simple_match = false;   // built by scg_plan_single (kaori::SimpleSingleMatch); a SINGLE plan of scg_plan_dual_single_end is not
     std::vector<int32_t> first1, first2;   // sequence uid -> first pool index (DuplicateAction::FIRST)
 
     // device state
@@ -417,6 +418,7 @@ struct RandomKeys {
 RandomKeys random_keys_with_ids(scg_plan* P);
 void launch_batch(scg_plan* P, const ScgReads& R, int64_t n, hipStream_t stream);
 void launch_batch_paired(scg_plan* P, const ScgReads& R1, const ScgReads& R2, int64_t n, hipStream_t stream);
+void launch_batch_assign(scg_plan* P, const ScgReads& R, int64_t n, const ScgAssignOut& out, hipStream_t stream);
 
 // ---- scg_files.cpp ----
 // ---- FASTQ -> device staging: two slots, each with its own stream, pinned and device buffers ----

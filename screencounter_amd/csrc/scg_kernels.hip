@@ -8,6 +8,7 @@
 // kaori handler's process() (paths relative to inst/include/kaori/handlers/ in the reference):
 //   single_kernel <- SingleBarcodeSingleEnd::process          SingleBarcodeSingleEnd.hpp:93-104
 //                    + SimpleSingleMatch::search_first/best    ../SimpleSingleMatch.hpp:200-306
+//   assign_kernel <- the same search, its whole State kept     ../SimpleSingleMatch.hpp:103-140
 //   single_paired_kernel <- SingleBarcodePairedEnd::process   SingleBarcodePairedEnd.hpp:93-124
 //   combo_kernel  <- CombinatorialBarcodesSingleEnd::process   CombinatorialBarcodesSingleEnd.hpp:149-258
 //   dual_kernel   <- DualBarcodesPairedEnd::process            DualBarcodesPairedEnd.hpp:228-381
@@ -40,21 +41,46 @@ constexpr int BLOCK = 256;
 
 // ---------------------------------------------------------------------------------------------
 // Match policies of the handlers' "best" searches and the two ways a result leaves a kernel.  Each is shared by the
-// general and the staged function of its handler; the use_first exits stay in the loops.
+// general and the staged function of its handler; the use_first exits stay in the loops (single: through the policy's first()).
 // ---------------------------------------------------------------------------------------------
 // SimpleSingleMatch::search_best (SimpleSingleMatch.hpp:265-289): the fewest mismatches win, a tie between two
 // different barcodes is no match.  Start from {max_mm + 1, -1, false}; `best` is the winner's mismatches when found.
+// As a hit policy of single_read / single_read_staged (which hand offer() and first() the window's position p, strand
+// and barcode mismatches d as well): the result is the barcode's index alone.
 struct BestSingle {
+    typedef int Result;
     int best, index;
     bool found;
-    __device__ __forceinline__ void offer(int idx, int tot) {
+    static __device__ __forceinline__ BestSingle start(int max_mm) { return BestSingle{max_mm + 1, -1, false}; }
+    __device__ __forceinline__ void offer(int idx, int tot, int = 0, int = 0, bool = false) {
         if (tot == best) {
             if (index != idx) { found = false; index = -1; }
         } else if (tot < best) {
             found = true; best = tot; index = idx;
         }
     }
+    // first mode: the first hit is the result (SimpleSingleMatch.hpp:207-224)
+    static __device__ __forceinline__ int first(int idx, int, int, int, bool) { return idx; }
     __device__ __forceinline__ int result() const { return found ? index : -1; }
+};
+
+// The same policy keeping all of SimpleSingleMatch::State (SimpleSingleMatch.hpp:103-140): where and how the hit was made is
+// taken with the index, i.e. only on `tot < best` (:276-288) -- a later equal hit of the same barcode keeps the first
+// position, one of another barcode leaves no match until a strictly better hit follows -- or from the first hit (:217-222).
+struct BestSingleState {
+    typedef BestSingleState Result;
+    int best, index, position, variable;
+    bool found, reverse;
+    static __device__ __forceinline__ BestSingleState start(int max_mm) { return BestSingleState{max_mm + 1, -1, -1, -1, false, false}; }
+    __device__ __forceinline__ void offer(int idx, int tot, int d, int p, bool rev) {
+        if (tot == best) {
+            if (index != idx) { found = false; index = -1; }
+        } else if (tot < best) {
+            found = true; best = tot; index = idx; variable = d; position = p; reverse = rev;
+        }
+    }
+    static __device__ __forceinline__ BestSingleState first(int idx, int tot, int d, int p, bool rev) { return BestSingleState{tot, idx, p, d, true, rev}; }
+    __device__ __forceinline__ BestSingleState result() const { return *this; }
 };
 
 // CombinatorialBarcodesSingleEnd.hpp:225-241: the same over a combination.  Start from {max_mm + 1, {0, 0}, false}.
@@ -153,14 +179,15 @@ __device__ __forceinline__ QueryT<W> pack_regions(const ScgTemplate* T, const ui
     return reverse ? reverse_complement(q, total_len) : q;
 }
 
-// `mismatches`, when asked for: those of the match returned (BestSingle::best; the paired handler's rule compares them
-// across mates).  Looked at only when the result is >= 0.
-template<class W = uint32_t>
-__device__ __forceinline__ int single_read(const ScgSingleParams& P, const Read& rd, int* mismatches = nullptr) {
+// The search of one read on its bytes, over a hit policy (BestSingle: the index; BestSingleState: the whole match state).
+// `mismatches`, when asked for: those of the match returned (the paired handler's rule compares them across mates).
+// Looked at only when the result is >= 0.
+template<class W = uint32_t, class Hit = BestSingle>
+__device__ __forceinline__ typename Hit::Result single_read(const ScgSingleParams& P, const Read& rd, int* mismatches = nullptr) {
     const ScgTemplate* T = P.tmpl;
     const int len = T->len;
     const int max_mm = P.max_mm;
-    BestSingle hit{max_mm + 1, -1, false};
+    Hit hit = Hit::start(max_mm);
     for (int p = 0; p + len <= rd.n; ++p) {
         for (int s = 0; s < 2; ++s) {                 // forward before reverse at each position
             if (s == 0 ? !P.fwd : !P.rev) continue;
@@ -172,9 +199,9 @@ __device__ __forceinline__ int single_read(const ScgSingleParams& P, const Read&
             if (idx < 0) continue;
             if (P.use_first) {                        // SimpleSingleMatch.hpp:207-224 (c + d <= max_mm by construction)
                 if (mismatches) *mismatches = c + d;
-                return idx;
+                return Hit::first(idx, c + d, d, p, s != 0);
             }
-            hit.offer(idx, c + d);
+            hit.offer(idx, c + d, d, p, s != 0);
         }
     }
     if (mismatches) *mismatches = hit.best;
@@ -206,6 +233,26 @@ __global__ __launch_bounds__(BLOCK) void single_paired_kernel(ScgSingleParams P,
         hit.offer(idx, mism);
     }
     emit_index(counts, i, hit.result());
+}
+
+// Read i's match state to the arrays asked for: consecutive lanes write consecutive elements of each.  No match: -1 in all.
+__device__ __forceinline__ void emit_state(const ScgAssignOut& out, int64_t i, const BestSingleState& hit) {
+    const bool f = hit.found;
+    out.index[i] = f ? hit.index : -1;
+    if (out.position) out.position[i] = f ? hit.position : -1;
+    if (out.mismatches) out.mismatches[i] = (int8_t)(f ? hit.best : -1);
+    if (out.variable_mismatches) out.variable_mismatches[i] = (int8_t)(f ? hit.variable : -1);
+    if (out.reverse) out.reverse[i] = (int8_t)(f ? (hit.reverse ? 1 : 0) : -1);
+}
+
+// SimpleSingleMatch::search_first / search_best per read, the whole State kept (scg_assign_batch): single_kernel's
+// search under the other hit policy, byte-wise.
+template<class W>
+__global__ __launch_bounds__(BLOCK) void assign_kernel(ScgSingleParams P, ScgReads R, int64_t n_reads, ScgAssignOut out) {
+    int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n_reads) return;
+    Read rd = get_read(R, i);
+    emit_state(out, i, single_read<W, BestSingleState>(P, rd));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -452,17 +499,17 @@ __global__ __launch_bounds__(BLOCK) void dual_kernel(ScgDualParams P, ScgReads R
 // =============================================================================================
 // W = uint32_t: one variable region of <= 32 bases (the hot configuration).  W = uint64_t: keys of up to
 // 64 bases, one region or several concatenated (wide barcodes, countDualBarcodesSingleEnd).
-template<int NW, int NT, int NC, class W>
-__device__ __forceinline__ int single_read_staged(const ScgSingleParams& P, const Tile<NW>& tile, const StrandTable<NT>& st, const StagedRead& sr, int ablate = 0,
-                                                  int* mismatches = nullptr) {
+template<int NW, int NT, int NC, class W, class Hit = BestSingle>
+__device__ __forceinline__ typename Hit::Result single_read_staged(const ScgSingleParams& P, const Tile<NW>& tile, const StrandTable<NT>& st, const StagedRead& sr,
+                                                                   int ablate = 0, int* mismatches = nullptr) {
     const ScgScan& T = P.scan;
     const int max_mm = P.max_mm;
     uint32_t candF[NC], candR[NC];
     scan_read<NW, NC>(tile, sr, T, P.fwd != 0, P.rev != 0, candF, candR);
 #ifdef SCG_ABLATE
-    if (ablate == 1) return (candF[0] ^ candR[NC - 1]) == 0x12345u ? 0 : -1;
+    if (ablate == 1) return Hit::first((candF[0] ^ candR[NC - 1]) == 0x12345u ? 0 : -1, 0, 0, 0, false);
 #endif
-    BestSingle hit{max_mm + 1, -1, false};
+    Hit hit = Hit::start(max_mm);
     const int last = last_position(sr.n, T.len);
     for (;;) {
         int p;
@@ -482,9 +529,9 @@ __device__ __forceinline__ int single_read_staged(const ScgSingleParams& P, cons
         if (idx < 0) continue;
         if (P.use_first) {
             if (mismatches) *mismatches = c + d;
-            return idx;
+            return Hit::first(idx, c + d, d, p, rev);
         }
-        hit.offer(idx, c + d);
+        hit.offer(idx, c + d, d, p, rev);
     }
     if (mismatches) *mismatches = hit.best;     // (as in single_read)
     return hit.result();
@@ -513,6 +560,40 @@ __global__ __launch_bounds__(STAGE_BLOCK, SCG_SINGLE_WAVES) __attribute__((amdgp
     idx = single_read_staged<NW, NT, NC, W>(P, tile, strands, sr);
 #endif
     emit_index(counts, lane_read(), idx);
+}
+
+// single_staged_kernel keeping the whole match state (scg_assign_batch): the same tile, strand table, staging call and LDS;
+// position, strand and barcode mismatches stay live across the walk beside the index, which does not fit the 64 VGPRs of
+// 8 waves per SIMD in every shape.  assign_waves: the highest bound at which the compiler reports no scratch
+// (profiles/assign_resource_usage.txt); the 320-base tiles are bounded by their LDS, not by registers.
+template<int NW, int NT, int NC, class W>
+constexpr int assign_waves() {
+#ifdef SCG_ASSIGN_WAVES       // (measurement builds: one bound for every shape)
+    return SCG_ASSIGN_WAVES;
+#else
+    // 160-base tiles under 129-256-base templates: at 8 waves (64 VGPRs) the compiler spills in these two shapes only; the
+    // second still does at 7 (72 VGPRs) and takes 73 when left 80
+    if (NW == 5 && NT == 8 && NC == 3 && sizeof(W) == 4) return 7;
+    if (NW == 5 && NT == 8 && NC == 5 && sizeof(W) == 8) return 6;
+    return 8;
+#endif
+}
+
+template<int NW, int NT, int NC, class W>
+__global__ __launch_bounds__(STAGE_BLOCK, (assign_waves<NW, NT, NC, W>())) __attribute__((amdgpu_num_sgpr(80))) void assign_staged_kernel(ScgSingleParams P, ScgReads R, int64_t n_reads,
+                                                                   ScgAssignOut out, int32_t* __restrict__ error_flag) {
+    __shared__ Tile<NW> tile;
+    __shared__ StrandTable<NT> strands;
+    fill_strand_table<NT>(strands, P.scan);
+    StagedRead sr;
+    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, sr);
+    if (lane == Lane::idle) return;
+    if (lane == Lane::unstaged) {
+        *error_flag = 1;
+        emit_state(out, lane_read(), BestSingleState::start(0));
+        return;
+    }
+    emit_state(out, lane_read(), single_read_staged<NW, NT, NC, W, BestSingleState>(P, tile, strands, sr));
 }
 
 // One barcode on either mate, in two passes over ONE tile (as dual_passes_kernel): mate 1 is staged, searched and reduced
@@ -1104,6 +1185,16 @@ template<int NW, int NT> struct LaunchSingle {
         return hipGetLastError();
     }
 };
+template<int NW, int NT> struct LaunchAssign {
+    static hipError_t go(const ScgSingleParams& P, const ScgReads& R, int64_t n, const ScgAssignOut& out, int32_t* flag, hipStream_t stream) {
+        const bool wide = P.index.wide || P.scan.nreg != 1;
+        with_shape<NW>(compact_fits<NW>(P.scan.compact_ok, R.max_len, P.scan.len), wide, [&](auto s) {
+            using S = decltype(s);
+            hipLaunchKernelGGL((assign_staged_kernel<NW, NT, S::NC, typename S::W>), dim3(staged_grid(n)), dim3(STAGE_BLOCK), extra_lds(), stream, P, R, n, out, flag);
+        });
+        return hipGetLastError();
+    }
+};
 template<int NW, int NT> struct LaunchSinglePaired {
     static hipError_t go(const ScgSingleParams& P, const ScgReads& R1, const ScgReads& R2, int64_t n, const ScgCounters& counts, int32_t* flag, hipStream_t stream) {
         const int max_len = R1.max_len > R2.max_len ? R1.max_len : R2.max_len;
@@ -1194,6 +1285,18 @@ hipError_t launch_single(const ScgSingleParams& P, int tmpl_len, const ScgReads&
         return hipGetLastError();
     }
     return dispatch_shape<LaunchSingle>(R.max_len, tmpl_len, P, R, n, counts, flag, stream);
+}
+
+// The batches launch_single gives each of its kernels, to the assign kernel of the same arguments.
+hipError_t launch_assign(const ScgSingleParams& P, int tmpl_len, const ScgReads& R, int64_t n, const ScgAssignOut& out, int32_t* flag, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    if (use_general(R.max_len) || P.index.wide == 2) {
+        with_key(P.index.wide ? P.index.wide : (int)(P.scan.nreg != 1), [&](auto s) {
+            hipLaunchKernelGGL((assign_kernel<typename decltype(s)::W>), dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R, n, out);
+        });
+        return hipGetLastError();
+    }
+    return dispatch_shape<LaunchAssign>(R.max_len, tmpl_len, P, R, n, out, flag, stream);
 }
 
 // SingleBarcodePairedEnd: the tile shape and the candidate mask go by the longer mate; a batch with a mate the staged

@@ -15,6 +15,8 @@ namespace scg {
 bool staged_takes(int max_len);
 
 hipError_t launch_single(const ScgSingleParams& P, int tmpl_len, const ScgReads& R, int64_t n, const ScgCounters& counts, int32_t* flag, hipStream_t stream);
+// kaori::SimpleSingleMatch::State of every read (scg_assign_batch): launch_single's dispatch, no counters touched
+hipError_t launch_assign(const ScgSingleParams& P, int tmpl_len, const ScgReads& R, int64_t n, const ScgAssignOut& out, int32_t* flag, hipStream_t stream);
 // kaori::SingleBarcodePairedEnd: the barcode of pair i is looked for on read i of R1 and of R2
 hipError_t launch_single_paired(const ScgSingleParams& P, int tmpl_len, const ScgReads& R1, const ScgReads& R2, int64_t n, const ScgCounters& counts, int32_t* flag,
                                 hipStream_t stream);

@@ -110,6 +110,7 @@ std::unique_ptr<scg_plan> compile_single(const char* constant, int strand, const
     P->n_counters = n_pool;
     P->max_mm1 = mismatches;
     P->use_first = use_first != 0;
+    P->simple_match = true;
     return P;
 }
 
@@ -788,6 +789,12 @@ void launch_batch(scg_plan* P, const ScgReads& R, int64_t n, hipStream_t stream)
     else if (tally) HIP_CHECK(scg::launch_tally(counts.unit_index, n, P->counters, P->n_counters, stream));
     else fold_replicas(P, stream);
     P->total += n;
+}
+
+// One batch of a single-barcode plan, assigned: launch_single's kernels under the state-keeping policy, writing to the
+// caller's arrays.  Counters, replicas, index streams and the total are not touched; only the error flag is shared.
+void launch_batch_assign(scg_plan* P, const ScgReads& R, int64_t n, const ScgAssignOut& out, hipStream_t stream) {
+    HIP_CHECK(scg::launch_assign(single_params(P, P->tab[0].view), P->ht1.t.len, R, n, out, P->error_flag.as<int32_t>(), stream));
 }
 
 // Paired-end kernels search each template on ONE strand, fixed per plan: they get the scan description with that strand in

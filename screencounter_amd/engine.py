@@ -10,6 +10,8 @@ torch is used only for device memory, streams and (in ``parallel``) torch.distri
 """
 from __future__ import annotations
 
+import collections
+import contextlib
 import ctypes as C
 from typing import Optional, Sequence
 
@@ -19,6 +21,10 @@ from . import _lib
 from ._lib import ScgError, check, cstr_array, errbuf
 
 STRANDS = {"original": 0, "reverse": 1, "both": 2}
+
+# Plan.assign: the fields of kaori::SimpleSingleMatch::State (SimpleSingleMatch.hpp:103-140), one array per field
+ASSIGN_FIELDS = ("index", "position", "mismatches", "variable_mismatches", "reverse")
+Assignment = collections.namedtuple("Assignment", ASSIGN_FIELDS)
 
 
 def _stream_handle(stream) -> int:
@@ -214,6 +220,38 @@ class Plan:
         err = errbuf()
         check(self._lib.scg_count_batch(self._h, C.c_void_p(_dev_ptr(seqs)), C.c_void_p(_dev_ptr(offsets)), int(fixed_len),
                                         int(max_len), int(n), C.c_void_p(_stream_handle(stream)), err, _lib.ERRCAP), err)
+
+    def assign(self, seqs, offsets=None, fixed_len: int = 0, n_reads: Optional[int] = None, stream=None, max_len: int = 0,
+               fields: Sequence[str] = ASSIGN_FIELDS) -> "Assignment":
+        """What each read of a batch matched (plans of Plan.single): kaori::SimpleSingleMatch::State per read, as an
+        ``Assignment`` of new tensors on the plan's device -- index and position int32, mismatches, variable_mismatches and
+        reverse int8, -1 everywhere for a read without a match; fields not named in ``fields`` are None (index is always
+        computed).  Batch arguments as for count(); asynchronous; the plan's counters and total are not touched."""
+        import torch
+        _check_u8(seqs, "seqs")
+        _check_offsets(offsets, "offsets")
+        unknown = [f for f in fields if f not in ASSIGN_FIELDS]
+        if unknown or "index" not in fields:
+            raise ValueError(f"fields must name 'index' and any of {ASSIGN_FIELDS[1:]} (got {tuple(fields)})")
+        if offsets is not None:
+            n = offsets.numel() - 1 if n_reads is None else n_reads
+            if max_len <= 0 and n > 0:
+                max_len = _max_len(offsets, n)
+        else:
+            if fixed_len <= 0:
+                raise ValueError("either offsets or a positive fixed_len is required")
+            n = seqs.numel() // fixed_len if n_reads is None else n_reads
+            if n * fixed_len > seqs.numel():
+                raise ValueError("seqs is shorter than n_reads * fixed_len")
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            # (allocated on the launch stream, so that the caching allocator orders their reuse with the kernel)
+            out = [torch.empty(int(n), dtype=torch.int32 if f in ("index", "position") else torch.int8, device=seqs.device)
+                   if f in fields else None for f in ASSIGN_FIELDS]
+        err = errbuf()
+        check(self._lib.scg_assign_batch(self._h, C.c_void_p(_dev_ptr(seqs)), C.c_void_p(_dev_ptr(offsets)), int(fixed_len),
+                                         int(max_len), int(n), *(C.c_void_p(_dev_ptr(t)) for t in out),
+                                         C.c_void_p(_stream_handle(stream)), err, _lib.ERRCAP), err)
+        return Assignment(*out)
 
     def count_paired(self, seqs1, seqs2, offsets1=None, offsets2=None, fixed_len1: int = 0, fixed_len2: int = 0,
                      n_pairs: Optional[int] = None, stream=None, max_len: int = 0) -> None:
