@@ -3,11 +3,18 @@
 The shared library is built in-tree by ``__graft_entry__.build()`` (or ``make -C
 screencounter_amd/csrc``).  There is no fallback of any kind: if the library is missing the
 import fails, and if no HIP device is present every counting call returns SCG_ERR_DEVICE.
+
+Besides the signatures: the marshalling steps that api.py and engine.py share, each written once -- strings and pools in
+(cstr_array, pool, cstr_matrix), combinations out (combo_outputs, per_file_combo_outputs) and sequence blobs out
+(decode_sequences).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
+
+import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SCG_LIB") or os.path.join(_HERE, "libscg.so")     # SCG_LIB: A/B builds (tools/ab.sh)
@@ -44,107 +51,76 @@ class SynthSpec(C.Structure):
     ]
 
 
+# Argument groups that recur in include/scg.h, so that a row below reads like the header's prototype.
+STR, INT, I32, I64, PTR = C.c_char_p, C.c_int, C.c_int32, C.c_int64, C.c_void_p
+ERR = [STR, C.c_size_t]                           # char* err, size_t errcap
+POOL = [c_str_p, I32]                             # const char* const* pool, int32_t n_pool
+POOLS = [C.POINTER(c_str_p), i32_p, I32]          # const char* const* const* pools, const int32_t* n_pools, int32_t n_regions
+COMBOS = [C.POINTER(i32_p), C.POINTER(i32_p), i64_p]     # int32_t** indices_out, int32_t** freq_out, int64_t* k_out (one entry, or one per file)
+READS = [PTR, PTR, I32]                           # const char* d_seqs, const uint32_t* d_offsets, int32_t fixed_len
+PLAN_OUT = C.POINTER(PTR)                         # scg_plan** plan_out
+
 # name -> (restype, argtypes); must list every symbol declared in include/scg.h
 SIGNATURES = {
-    "scg_version": (C.c_char_p, []),
-    "scg_device_count": (C.c_int, []),
-    "scg_set_device": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t]),
-    "scg_set_devices": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_char_p, C.c_size_t]),
-    "scg_count_single_barcodes": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, c_str_p, C.c_int32, C.c_int, C.c_int, C.c_int,
-                                            i32_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_count_combo_barcodes_single": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, c_str_p, C.c_int32, c_str_p, C.c_int32,
-                                                  C.c_int, C.c_int, C.c_int, C.POINTER(i32_p), C.POINTER(i32_p), i64_p, i32_p,
-                                                  C.c_char_p, C.c_size_t]),
-    "scg_count_dual_barcodes": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, c_str_p,
-                                          C.c_char_p, C.c_char_p, C.c_int, C.c_int, c_str_p, C.c_int32,
-                                          C.c_int, C.c_int, C.c_int, C.c_int, i32_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_count_single_barcodes_paired": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, c_str_p, C.c_int32, C.c_int, C.c_int, C.c_int,
-                                                   i32_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_count_single_barcodes_paired_files": (C.c_int, [c_str_p, c_str_p, C.c_int32, C.c_char_p, C.c_int, c_str_p, C.c_int32,
-                                                         C.c_int, C.c_int, C.c_int, i32_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_match_barcodes": (C.c_int, [c_str_p, C.c_int32, c_str_p, C.c_int32, C.c_int, C.c_int, i32_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_count_single_barcodes_files": (C.c_int, [c_str_p, C.c_int32, C.c_char_p, C.c_int, c_str_p, C.c_int32, C.c_int, C.c_int, C.c_int,
-                                                  i32_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_count_combo_barcodes_single_files": (C.c_int, [c_str_p, C.c_int32, C.c_char_p, C.c_int, c_str_p, C.c_int32, c_str_p, C.c_int32,
-                                                        C.c_int, C.c_int, C.c_int, C.POINTER(i32_p), C.POINTER(i32_p), i64_p, i32_p,
-                                                        C.c_char_p, C.c_size_t]),
-    "scg_count_dual_barcodes_files": (C.c_int, [c_str_p, C.c_char_p, C.c_int, C.c_int, c_str_p,
-                                                c_str_p, C.c_char_p, C.c_int, C.c_int, c_str_p, C.c_int32, C.c_int32,
-                                                C.c_int, C.c_int, C.c_int, i32_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_count_dual_barcodes_diagnostics_files": (C.c_int, [c_str_p, C.c_char_p, C.c_int, C.c_int, c_str_p,
-                                                            c_str_p, C.c_char_p, C.c_int, C.c_int, c_str_p, C.c_int32, C.c_int32,
-                                                            C.c_int, C.c_int, C.c_int, i32_p, C.POINTER(i32_p), C.POINTER(i32_p), i64_p,
-                                                            i32_p, i32_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_count_dual_barcodes_single_end_files": (C.c_int, [c_str_p, C.c_int32, C.c_char_p, C.POINTER(c_str_p), i32_p, C.c_int32,
-                                                           C.c_int, C.c_int, C.c_int, C.c_int, i32_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_count_dual_barcodes_single_end_diagnostics_files": (C.c_int, [c_str_p, C.c_int32, C.c_char_p, C.POINTER(c_str_p), i32_p, C.c_int32,
-                                                                       C.c_int, C.c_int, C.c_int, C.c_int, i32_p, C.POINTER(i32_p),
-                                                                       C.POINTER(i32_p), i64_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_count_combo_barcodes_paired_files": (C.c_int, [c_str_p, C.c_char_p, C.c_int, C.c_int, c_str_p, C.c_int32,
-                                                        c_str_p, C.c_char_p, C.c_int, C.c_int, c_str_p, C.c_int32, C.c_int32,
-                                                        C.c_int, C.c_int, C.c_int, C.POINTER(i32_p), C.POINTER(i32_p), i64_p,
-                                                        i32_p, i32_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_count_random_barcodes_files": (C.c_int, [c_str_p, C.c_int32, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                  C.POINTER(C.c_void_p), i64_p, i32_p, C.POINTER(i64_p), C.POINTER(i32_p), C.POINTER(i32_p),
-                                                  i32_p, C.c_char_p, C.c_size_t]),
-    "scg_fastq_text_windows": (C.c_int, [C.c_char_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p), i64_p, C.POINTER(C.c_void_p), i64_p,
-                                         C.c_char_p, C.c_char_p, C.c_size_t]),
-    "scg_fastq_scan_windows": (C.c_int, [C.c_char_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), i64_p, i64_p,
-                                         C.c_char_p, C.c_size_t]),
-    "scg_bgzf_member_batches": (C.c_int, [C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_void_p), i64_p, C.POINTER(C.c_void_p), i64_p, i64_p,
-                                          C.c_char_p, C.c_size_t]),
-    "scg_free": (None, [C.c_void_p]),
+    "scg_version": (STR, []),
+    "scg_device_count": (INT, []),
+    "scg_set_device": (INT, [INT, *ERR]),
+    "scg_set_devices": (INT, [C.POINTER(INT), INT, *ERR]),
+    "scg_count_single_barcodes": (INT, [STR, STR, INT, *POOL, INT, INT, INT, i32_p, i32_p, *ERR]),
+    "scg_count_combo_barcodes_single": (INT, [STR, STR, INT, *POOL, *POOL, INT, INT, INT, *COMBOS, i32_p, *ERR]),
+    "scg_count_dual_barcodes": (INT, [STR, STR, INT, INT, c_str_p, STR, STR, INT, INT, c_str_p, I32,
+                                      INT, INT, INT, INT, i32_p, i32_p, *ERR]),
+    "scg_count_single_barcodes_paired": (INT, [STR, STR, STR, INT, *POOL, INT, INT, INT, i32_p, i32_p, *ERR]),
+    "scg_count_single_barcodes_paired_files": (INT, [c_str_p, c_str_p, I32, STR, INT, *POOL, INT, INT, INT, i32_p, i32_p, *ERR]),
+    "scg_match_barcodes": (INT, [*POOL, *POOL, INT, INT, i32_p, i32_p, *ERR]),
+    "scg_count_single_barcodes_files": (INT, [c_str_p, I32, STR, INT, *POOL, INT, INT, INT, i32_p, i32_p, *ERR]),
+    "scg_count_combo_barcodes_single_files": (INT, [c_str_p, I32, STR, INT, *POOL, *POOL, INT, INT, INT, *COMBOS, i32_p, *ERR]),
+    "scg_count_dual_barcodes_files": (INT, [c_str_p, STR, INT, INT, c_str_p, c_str_p, STR, INT, INT, c_str_p, I32, I32,
+                                            INT, INT, INT, i32_p, i32_p, *ERR]),
+    "scg_count_dual_barcodes_diagnostics_files": (INT, [c_str_p, STR, INT, INT, c_str_p, c_str_p, STR, INT, INT, c_str_p, I32, I32,
+                                                        INT, INT, INT, i32_p, *COMBOS, i32_p, i32_p, i32_p, *ERR]),
+    "scg_count_dual_barcodes_single_end_files": (INT, [c_str_p, I32, STR, *POOLS, INT, INT, INT, INT, i32_p, i32_p, *ERR]),
+    "scg_count_dual_barcodes_single_end_diagnostics_files": (INT, [c_str_p, I32, STR, *POOLS, INT, INT, INT, INT, i32_p, *COMBOS, i32_p, *ERR]),
+    "scg_count_combo_barcodes_paired_files": (INT, [c_str_p, STR, INT, INT, *POOL, c_str_p, STR, INT, INT, *POOL, I32,
+                                                    INT, INT, INT, *COMBOS, i32_p, i32_p, i32_p, *ERR]),
+    "scg_count_random_barcodes_files": (INT, [c_str_p, I32, STR, INT, INT, INT, INT,
+                                              C.POINTER(PTR), i64_p, i32_p, C.POINTER(i64_p), C.POINTER(i32_p), C.POINTER(i32_p), i32_p, *ERR]),
+    "scg_fastq_text_windows": (INT, [STR, I64, INT, C.POINTER(PTR), i64_p, C.POINTER(PTR), i64_p, STR, *ERR]),
+    "scg_fastq_scan_windows": (INT, [STR, I64, INT, C.POINTER(PTR), C.POINTER(PTR), i64_p, i64_p, *ERR]),
+    "scg_bgzf_member_batches": (INT, [STR, I64, I64, INT, C.POINTER(PTR), i64_p, C.POINTER(PTR), i64_p, i64_p, *ERR]),
+    "scg_free": (None, [PTR]),
     "scg_release_buffers": (None, []),
-    "scg_parse_fastq": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), i64_p, C.c_char_p, C.c_size_t]),
-    "scg_plan_single": (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, c_str_p, C.c_int32, C.c_int, C.c_int, C.c_int,
-                                  C.c_char_p, C.c_size_t]),
-    "scg_plan_single_paired": (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, c_str_p, C.c_int32, C.c_int, C.c_int, C.c_int,
-                                         C.c_char_p, C.c_size_t]),
-    "scg_plan_combo": (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, c_str_p, C.c_int32, c_str_p, C.c_int32, C.c_int, C.c_int,
-                                 C.c_int, C.c_char_p, C.c_size_t]),
-    "scg_plan_dual": (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, C.c_int, c_str_p, C.c_char_p, C.c_int, C.c_int, c_str_p,
-                                C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
-    "scg_count_dual_barcodes_diagnostics": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, c_str_p,
-                                                      C.c_char_p, C.c_char_p, C.c_int, C.c_int, c_str_p, C.c_int32,
-                                                      C.c_int, C.c_int, C.c_int, i32_p, C.POINTER(i32_p), C.POINTER(i32_p), i64_p,
-                                                      i32_p, i32_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_count_random_barcodes": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
-                                            C.POINTER(i32_p), i64_p, i32_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_count_dual_barcodes_single_end": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(c_str_p), i32_p, C.c_int32,
-                                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_count_dual_barcodes_single_end_diagnostics": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(c_str_p), i32_p, C.c_int32,
-                                                                 C.c_int, C.c_int, C.c_int, C.c_int, i32_p, C.POINTER(i32_p), C.POINTER(i32_p),
-                                                                 i64_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_plan_dual_single_end": (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, C.POINTER(c_str_p), i32_p, C.c_int32,
-                                           C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
-    "scg_count_combo_barcodes_paired": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, c_str_p, C.c_int32,
-                                                  C.c_char_p, C.c_char_p, C.c_int, C.c_int, c_str_p, C.c_int32,
-                                                  C.c_int, C.c_int, C.c_int, C.POINTER(i32_p), C.POINTER(i32_p), i64_p,
-                                                  i32_p, i32_p, i32_p, C.c_char_p, C.c_size_t]),
-    "scg_plan_paired_combo": (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, C.c_int, c_str_p, C.c_int32,
-                                        C.c_char_p, C.c_int, C.c_int, c_str_p, C.c_int32,
-                                        C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
-    "scg_plan_read_diagnostics": (C.c_int, [C.c_void_p, i32_p, C.POINTER(i32_p), C.POINTER(i32_p), i64_p, i64_p, i32_p, i32_p,
-                                            C.c_void_p, C.c_char_p, C.c_size_t]),
-    "scg_plan_random": (C.c_int, [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
-    "scg_plan_read_random": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(i32_p), i64_p, i32_p, i64_p, C.c_void_p,
-                                       C.c_char_p, C.c_size_t]),
-    "scg_plan_destroy": (None, [C.c_void_p]),
-    "scg_plan_num_counters": (C.c_int64, [C.c_void_p]),
-    "scg_plan_device_counters": (C.c_void_p, [C.c_void_p]),
-    "scg_plan_bind_counters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
-    "scg_plan_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
-    "scg_count_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_char_p, C.c_size_t]),
-    "scg_count_batch_paired": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
-                                         C.c_int32, C.c_int64, C.c_void_p, C.c_char_p, C.c_size_t]),
-    "scg_assign_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
-    "scg_plan_read": (C.c_int, [C.c_void_p, i32_p, i64_p, C.c_void_p, C.c_char_p, C.c_size_t]),
-    "scg_plan_read_combinations": (C.c_int, [C.c_void_p, C.POINTER(i32_p), C.POINTER(i32_p), i64_p, i64_p, C.c_void_p, C.c_char_p, C.c_size_t]),
-    "scg_combo_compact": (C.c_int, [i32_p, C.c_int32, C.c_int32, C.POINTER(i32_p), C.POINTER(i32_p), i64_p, C.c_char_p, C.c_size_t]),
-    "scg_plan_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
-    "scg_plan_kernel_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), i64_p, C.c_char_p, C.c_size_t]),
-    "scg_synth_reads": (C.c_int, [C.POINTER(SynthSpec), C.c_void_p, C.c_int64, C.c_void_p, C.c_char_p, C.c_size_t]),
+    "scg_parse_fastq": (INT, [STR, C.POINTER(PTR), C.POINTER(PTR), i64_p, *ERR]),
+    "scg_plan_single": (INT, [PLAN_OUT, STR, INT, *POOL, INT, INT, INT, *ERR]),
+    "scg_plan_single_paired": (INT, [PLAN_OUT, STR, INT, *POOL, INT, INT, INT, *ERR]),
+    "scg_plan_combo": (INT, [PLAN_OUT, STR, INT, *POOL, *POOL, INT, INT, INT, *ERR]),
+    "scg_plan_dual": (INT, [PLAN_OUT, STR, INT, INT, c_str_p, STR, INT, INT, c_str_p, I32, INT, INT, INT, INT, *ERR]),
+    "scg_count_dual_barcodes_diagnostics": (INT, [STR, STR, INT, INT, c_str_p, STR, STR, INT, INT, c_str_p, I32,
+                                                  INT, INT, INT, i32_p, *COMBOS, i32_p, i32_p, i32_p, *ERR]),
+    "scg_count_random_barcodes": (INT, [STR, STR, INT, INT, INT, INT, C.POINTER(PTR), C.POINTER(i32_p), i64_p, i32_p, i32_p, *ERR]),
+    "scg_count_dual_barcodes_single_end": (INT, [STR, STR, *POOLS, INT, INT, INT, INT, INT, i32_p, i32_p, *ERR]),
+    "scg_count_dual_barcodes_single_end_diagnostics": (INT, [STR, STR, *POOLS, INT, INT, INT, INT, i32_p, *COMBOS, i32_p, *ERR]),
+    "scg_plan_dual_single_end": (INT, [PLAN_OUT, STR, INT, *POOLS, INT, INT, INT, *ERR]),
+    "scg_count_combo_barcodes_paired": (INT, [STR, STR, INT, INT, *POOL, STR, STR, INT, INT, *POOL,
+                                              INT, INT, INT, *COMBOS, i32_p, i32_p, i32_p, *ERR]),
+    "scg_plan_paired_combo": (INT, [PLAN_OUT, STR, INT, INT, *POOL, STR, INT, INT, *POOL, INT, INT, INT, *ERR]),
+    "scg_plan_read_diagnostics": (INT, [PTR, i32_p, *COMBOS, i64_p, i32_p, i32_p, PTR, *ERR]),
+    "scg_plan_random": (INT, [PLAN_OUT, STR, INT, INT, INT, INT, *ERR]),
+    "scg_plan_read_random": (INT, [PTR, C.POINTER(PTR), C.POINTER(i32_p), i64_p, i32_p, i64_p, PTR, *ERR]),
+    "scg_plan_destroy": (None, [PTR]),
+    "scg_plan_num_counters": (I64, [PTR]),
+    "scg_plan_device_counters": (PTR, [PTR]),
+    "scg_plan_bind_counters": (INT, [PTR, PTR, *ERR]),
+    "scg_plan_reset": (INT, [PTR, PTR, *ERR]),
+    "scg_count_batch": (INT, [PTR, *READS, I32, I64, PTR, *ERR]),
+    "scg_count_batch_paired": (INT, [PTR, *READS, *READS, I32, I64, PTR, *ERR]),
+    "scg_assign_batch": (INT, [PTR, *READS, I32, I64, PTR, PTR, PTR, PTR, PTR, PTR, *ERR]),
+    "scg_plan_read": (INT, [PTR, i32_p, i64_p, PTR, *ERR]),
+    "scg_plan_read_combinations": (INT, [PTR, *COMBOS, i64_p, PTR, *ERR]),
+    "scg_combo_compact": (INT, [i32_p, I32, I32, *COMBOS, *ERR]),
+    "scg_plan_set_profiling": (INT, [PTR, INT]),
+    "scg_plan_kernel_stats": (INT, [PTR, C.POINTER(C.c_double), i64_p, *ERR]),
+    "scg_synth_reads": (INT, [C.POINTER(SynthSpec), PTR, I64, PTR, *ERR]),
 }
 
 _lib = None
@@ -229,3 +205,44 @@ def cstr_array(strings):
         keep.append(b)
         arr[i] = b
     return arr, keep
+
+
+def pool(strings):
+    """A pool as the header takes it: (const char* const* pool, int32_t n_pool).  (The array holds on to its strings.)"""
+    return cstr_array(strings)[0], len(strings)
+
+
+@contextlib.contextmanager
+def per_file_combo_outputs(L, n: int):
+    """The caller-allocated arrays of n entries for the malloc'd combinations of a many-files entry (int32_t** indices_out,
+    int32_t** freq_out, int64_t* k_out).  `with ... as (outputs, take)`: pass `*outputs` to the call; after it, take() is a
+    list of n (indices int32[2, K_f], freq int32[K_f]), fresh arrays that own their memory, (2, 0) and (0,) where K_f is 0.
+    Leaving the block frees every pointer the C side handed out, whatever happened inside: a call that failed, an
+    exception while copying."""
+    idx, freq, ks = (i32_p * max(n, 1))(), (i32_p * max(n, 1))(), (C.c_int64 * max(n, 1))()
+
+    def copies(f):
+        K = int(ks[f])
+        if K == 0:                                   # (nothing to read: the pointers are not looked at)
+            return np.zeros((2, 0), dtype=np.int32), np.zeros(0, dtype=np.int32)
+        return np.ctypeslib.as_array(idx[f], shape=(K, 2)).T.copy(), np.ctypeslib.as_array(freq[f], shape=(K,)).copy()
+    try:
+        yield (idx, freq, ks), lambda: [copies(f) for f in range(n)]
+    finally:
+        for f in range(n):
+            L.scg_free(idx[f])
+            L.scg_free(freq[f])
+
+
+@contextlib.contextmanager
+def combo_outputs(L):
+    """The same for the three outputs of an entry that returns one set of combinations -- the per-file arrays with one
+    entry: take() -> (indices int32[2, K], freq int32[K])."""
+    with per_file_combo_outputs(L, 1) as (outputs, take):
+        yield outputs, lambda: take()[0]
+
+
+def decode_sequences(ptr, K: int, W: int):
+    """K sequences of width W, NUL-terminated (stride W + 1) -> list[str], decoded as latin-1."""
+    blob = C.string_at(ptr, K * (W + 1)) if K else b""
+    return [blob[i * (W + 1): i * (W + 1) + W].decode("latin-1") for i in range(K)]

@@ -8,6 +8,10 @@ reference and are not part of this package; the tests keep a small mirror of the
 reference's own test vectors can be written the way its tests write them.
 
 Everything is computed by libscg on the GPU; errors the reference raises as R errors surface as ``ScgError``.
+
+Every function reads: checks the reference makes before anything else, the outputs, the native call, the result's shape.
+The marshalling steps are _lib's (pools, combinations, sequence blobs); what the many-files entries share is
+_files_call and _files_counts below.
 """
 from __future__ import annotations
 
@@ -19,22 +23,32 @@ from typing import Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import ScgError, check, cstr_array, errbuf
+from ._lib import ERRCAP, ScgError, check, combo_outputs, cstr_array, cstr_matrix, errbuf, i32_p, per_file_combo_outputs
+
+TWO_REGIONS = "currently expecting only 2 variable regions for single-end combinatorial barcodes"   # src/count_combo_barcodes_single.cpp:44-46
+SAME_LENGTH = "both barcode pools should be of the same length"                                     # kaori/handlers/DualBarcodesPairedEnd.hpp:106-109
+
+
+def _int32_out(n: int):
+    """A caller-allocated int32[n] output -> (the array, its pointer for the call); the result is `array[:n].copy()`."""
+    out = np.zeros(max(n, 1), dtype=np.int32)
+    return out, out.ctypes.data_as(i32_p)
+
+
+def _path(path) -> bytes:
+    return os.fspath(path).encode()
+
 
 # =============================================================================================
-# Rcpp level
+# Rcpp level: one file (or one pair of files)
 # =============================================================================================
 def count_single_barcodes(path: str, constant: str, strand: int, pool: Sequence[str], mismatches: int,
                           use_first: bool, nthreads: int = 1):
     """src/count_single_barcodes.cpp:28-50 -> (counts int32[len(pool)], total)."""
-    L = _lib.load()
-    counts = np.zeros(max(len(pool), 1), dtype=np.int32)
-    total = C.c_int32(0)
-    err = errbuf()
-    parr, _keep = cstr_array(pool)
-    check(L.scg_count_single_barcodes(os.fspath(path).encode(), constant.encode(), int(strand), parr, len(pool),
-                                      int(mismatches), int(bool(use_first)), int(nthreads),
-                                      counts.ctypes.data_as(_lib.i32_p), C.byref(total), err, _lib.ERRCAP), err)
+    L, err = _lib.load(), errbuf()
+    (counts, counts_p), total = _int32_out(len(pool)), C.c_int32(0)
+    check(L.scg_count_single_barcodes(_path(path), constant.encode(), int(strand), *_lib.pool(pool),
+                                      int(mismatches), int(bool(use_first)), int(nthreads), counts_p, C.byref(total), err, ERRCAP), err)
     return counts[:len(pool)].copy(), int(total.value)
 
 
@@ -42,29 +56,107 @@ def count_combo_barcodes_single(path: str, constant: str, strand: int, pool: Seq
                                 use_first: bool, nthreads: int = 1):
     """src/count_combo_barcodes_single.cpp:39-70 -> (indices int32[2, K] 0-based, freq int32[K], total)."""
     if len(pool) != 2:
-        # src/count_combo_barcodes_single.cpp:44-46
-        raise ScgError(_lib.SCG_ERR_INVALID, "currently expecting only 2 variable regions for single-end combinatorial barcodes")
-    L = _lib.load()
-    idx_p = _lib.i32_p()
-    freq_p = _lib.i32_p()
-    k = C.c_int64(0)
+        raise ScgError(_lib.SCG_ERR_INVALID, TWO_REGIONS)
+    L, err = _lib.load(), errbuf()
     total = C.c_int32(0)
-    err = errbuf()
-    p0, _k0 = cstr_array(pool[0])
-    p1, _k1 = cstr_array(pool[1])
-    check(L.scg_count_combo_barcodes_single(os.fspath(path).encode(), constant.encode(), int(strand), p0, len(pool[0]), p1, len(pool[1]),
-                                            int(mismatches), int(bool(use_first)), int(nthreads),
-                                            C.byref(idx_p), C.byref(freq_p), C.byref(k), C.byref(total), err, _lib.ERRCAP), err)
+    with combo_outputs(L) as (combos, take):
+        check(L.scg_count_combo_barcodes_single(_path(path), constant.encode(), int(strand), *_lib.pool(pool[0]), *_lib.pool(pool[1]),
+                                                int(mismatches), int(bool(use_first)), int(nthreads), *combos, C.byref(total), err, ERRCAP), err)
+        idx, freq = take()
+    return idx, freq, int(total.value)
+
+
+def count_single_barcodes_paired(path1: str, path2: str, constant: str, strand: int, pool: Sequence[str], mismatches: int, use_first: bool,
+                                 nthreads: int = 1):
+    """kaori::SingleBarcodePairedEnd (handlers/SingleBarcodePairedEnd.hpp:93-124) over two files: the barcode of a pair is
+    looked for on either mate -> (counts int32[len(pool)], total pairs)."""
+    L, err = _lib.load(), errbuf()
+    (counts, counts_p), total = _int32_out(len(pool)), C.c_int32(0)
+    check(L.scg_count_single_barcodes_paired(_path(path1), _path(path2), constant.encode(), int(strand), *_lib.pool(pool),
+                                             int(mismatches), int(bool(use_first)), int(nthreads), counts_p, C.byref(total), err, ERRCAP), err)
+    return counts[:len(pool)].copy(), int(total.value)
+
+
+def count_dual_barcodes(path1: str, constant1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],
+                        path2: str, constant2: str, reverse2: bool, mismatches2: int, pool2: Sequence[str],
+                        randomized: bool, use_first: bool, diagnostics: bool = False, nthreads: int = 1):
+    """src/count_dual_barcodes.cpp:74-117 -> (counts int32[n pairs], total), or with diagnostics=True the
+    five outputs of the include.invalid=TRUE branch: (counts, (indices int32[2, K] 0-based, freq), total,
+    barcode1_only, barcode2_only)."""
+    if len(pool1) != len(pool2):
+        raise ScgError(_lib.SCG_ERR_INVALID, SAME_LENGTH)
+    L, err = _lib.load(), errbuf()
+    (counts, counts_p), total = _int32_out(len(pool1)), C.c_int32(0)
+    sides = (_path(path1), constant1.encode(), int(bool(reverse1)), int(mismatches1), cstr_array(pool1)[0],
+             _path(path2), constant2.encode(), int(bool(reverse2)), int(mismatches2), cstr_array(pool2)[0], len(pool1))
+    if diagnostics:
+        b1, b2 = C.c_int32(0), C.c_int32(0)
+        with combo_outputs(L) as (combos, take):
+            check(L.scg_count_dual_barcodes_diagnostics(*sides, int(bool(randomized)), int(bool(use_first)), int(nthreads), counts_p, *combos,
+                                                        C.byref(total), C.byref(b1), C.byref(b2), err, ERRCAP), err)
+            invalid = take()
+        return counts[:len(pool1)].copy(), invalid, int(total.value), int(b1.value), int(b2.value)
+    check(L.scg_count_dual_barcodes(*sides, int(bool(randomized)), int(bool(use_first)), int(bool(diagnostics)), int(nthreads),
+                                    counts_p, C.byref(total), err, ERRCAP), err)
+    return counts[:len(pool1)].copy(), int(total.value)
+
+
+def count_random_barcodes(path: str, constant: str, strand: int, mismatches: int, use_first: bool, nthreads: int = 1):
+    """src/count_random_barcodes.cpp:41-62 -> ((sequences list[str] sorted, freq int32[K]), total)."""
+    L, err = _lib.load(), errbuf()
+    seq_p, freq_p = C.c_void_p(), i32_p()
+    k, vlen, total = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+    check(L.scg_count_random_barcodes(_path(path), constant.encode(), int(strand), int(mismatches), int(bool(use_first)),
+                                      int(nthreads), C.byref(seq_p), C.byref(freq_p), C.byref(k), C.byref(vlen), C.byref(total), err, ERRCAP), err)
     K = int(k.value)
     try:
-        idx = np.ctypeslib.as_array(idx_p, shape=(max(2 * K, 1),))[:2 * K].reshape(K, 2).T.copy()
+        seqs = _lib.decode_sequences(seq_p, K, int(vlen.value))
         freq = np.ctypeslib.as_array(freq_p, shape=(max(K, 1),))[:K].copy()
     finally:
-        L.scg_free(idx_p)
+        L.scg_free(seq_p)
         L.scg_free(freq_p)
-    return idx.astype(np.int32), freq.astype(np.int32), int(total.value)
+    return (seqs, freq), int(total.value)
 
 
+def count_dual_barcodes_single_end(path: str, constant: str, pools: Sequence[Sequence[str]], strand: int, mismatches: int,
+                                   use_first: bool, diagnostics: bool = False, nthreads: int = 1):
+    """src/count_dual_barcodes_single_end.cpp:53-87 -> (counts int32[n combinations], total), or with diagnostics=True
+    (counts, (indices int32[2, K] 0-based, freq), total) as in its include.invalid=TRUE branch."""
+    L, err = _lib.load(), errbuf()
+    nch = len(pools[0]) if pools else 0
+    (counts, counts_p), total = _int32_out(nch), C.c_int32(0)
+    rows, sizes, _keep = cstr_matrix(pools)
+    if diagnostics:
+        with combo_outputs(L) as (combos, take):
+            check(L.scg_count_dual_barcodes_single_end_diagnostics(_path(path), constant.encode(), rows, sizes, len(pools), int(strand),
+                                                                   int(mismatches), int(bool(use_first)), int(nthreads), counts_p, *combos,
+                                                                   C.byref(total), err, ERRCAP), err)
+            invalid = take()
+        return counts[:nch].copy(), invalid, int(total.value)
+    check(L.scg_count_dual_barcodes_single_end(_path(path), constant.encode(), rows, sizes, len(pools), int(strand), int(mismatches),
+                                               int(bool(use_first)), int(bool(diagnostics)), int(nthreads), counts_p, C.byref(total), err, ERRCAP), err)
+    return counts[:nch].copy(), int(total.value)
+
+
+def count_combo_barcodes_paired(path1: str, constant1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],
+                                path2: str, constant2: str, reverse2: bool, mismatches2: int, pool2: Sequence[str],
+                                randomized: bool, use_first: bool, nthreads: int = 1):
+    """src/count_combo_barcodes_paired.cpp:57-95 -> (indices int32[2, K] 0-based sorted by (first, second),
+    freq int32[K], total, barcode1_only, barcode2_only)."""
+    L, err = _lib.load(), errbuf()
+    total, b1, b2 = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    with combo_outputs(L) as (combos, take):
+        check(L.scg_count_combo_barcodes_paired(_path(path1), constant1.encode(), int(bool(reverse1)), int(mismatches1), *_lib.pool(pool1),
+                                                _path(path2), constant2.encode(), int(bool(reverse2)), int(mismatches2), *_lib.pool(pool2),
+                                                int(bool(randomized)), int(bool(use_first)), int(nthreads), *combos,
+                                                C.byref(total), C.byref(b1), C.byref(b2), err, ERRCAP), err)
+        idx, freq = take()
+    return idx, freq, int(total.value), int(b1.value), int(b2.value)
+
+
+# =============================================================================================
+# Many files in one native call (matrixOf*)
+# =============================================================================================
 @contextlib.contextmanager
 def _devices_env(devices):
     """`devices=` of the matrixOf* mirrors -> scg_set_devices for the duration of one native call on this thread (the C
@@ -77,81 +169,55 @@ def _devices_env(devices):
     err = errbuf()
     ids = [int(d) for d in devices]
     arr = (C.c_int * max(len(ids), 1))(*ids)
-    check(L.scg_set_devices(arr, len(ids), err, _lib.ERRCAP), err)
+    check(L.scg_set_devices(arr, len(ids), err, ERRCAP), err)
     try:
         yield
     finally:
-        L.scg_set_devices(None, 0, err, _lib.ERRCAP)
+        L.scg_set_devices(None, 0, err, ERRCAP)
+
+
+@contextlib.contextmanager
+def _files_call(devices, *path_lists, scalars: int = 1):
+    """What the many-files mirrors share around their native call.  `with ... as (n, paths, outs)`: n files; `paths`, one C
+    array per list of paths; `outs`, `scalars` caller-allocated int32 arrays of n entries (totals; barcode1_only,
+    barcode2_only), read afterwards as `out[:n]`, a list.  Every array has at least one entry, and `devices` is the C ABI's
+    device list while the block runs."""
+    n = len(path_lists[0])
+    paths = [cstr_array([os.fspath(x) for x in p])[0] for p in path_lists]
+    outs = [(C.c_int32 * max(n, 1))() for _ in range(scalars)]
+    with _devices_env(devices):
+        yield n, paths, outs
+
+
+def _files_counts(n_pool: int, n_files: int):
+    """The column-major int32[n_pool, n_files] output of a many-files entry (column f = file f) -> (its pointer for the
+    call, take() -> a copy shaped [n_pool, n_files])."""
+    buf = np.zeros(max(n_pool * n_files, 1), dtype=np.int32)
+    return buf.ctypes.data_as(i32_p), lambda: buf[:n_pool * n_files].reshape(n_files, n_pool).T.copy()
 
 
 def count_single_barcodes_files(paths: Sequence[str], constant: str, strand: int, pool: Sequence[str], mismatches: int,
                                 use_first: bool, nthreads: int = 1, devices=None):
     """scg_count_single_barcodes_files: every file of matrixOfSingleBarcodes in one native call
     -> (counts int32[len(pool), len(paths)], totals list)."""
-    L = _lib.load()
-    n = len(paths)
-    counts = np.zeros((max(n, 1), max(len(pool), 1)), dtype=np.int32)      # row f = column f of the column-major output
-    totals = (C.c_int32 * max(n, 1))()
-    err = errbuf()
-    parr, _keep = cstr_array(pool)
-    farr, _fk = cstr_array([os.fspath(x) for x in paths])
-    with _devices_env(devices):
-        check(L.scg_count_single_barcodes_files(farr, n, constant.encode(), int(strand), parr, len(pool), int(mismatches),
-                                                int(bool(use_first)), int(nthreads), _files_out(counts, len(pool)), totals,
-                                                err, _lib.ERRCAP), err)
-    return _files_matrix(counts, len(pool), n), [int(totals[i]) for i in range(n)]
-
-
-def _files_out(buf: np.ndarray, n_pool: int):
-    """A contiguous int32 buffer of n_pool * n_files entries inside `buf` (allocated with >= 1 row / column)."""
-    return buf.reshape(-1).ctypes.data_as(_lib.i32_p)
-
-
-def _files_matrix(buf: np.ndarray, n_pool: int, n_files: int) -> np.ndarray:
-    flat = buf.reshape(-1)[: n_pool * n_files]
-    return flat.reshape(n_files, n_pool).T.copy()          # column-major n_pool x n_files -> [n_pool, n_files]
+    L, err = _lib.load(), errbuf()
+    counts_p, take_counts = _files_counts(len(pool), len(paths))
+    with _files_call(devices, paths) as (n, (farr,), (totals,)):
+        check(L.scg_count_single_barcodes_files(farr, n, constant.encode(), int(strand), *_lib.pool(pool), int(mismatches),
+                                                int(bool(use_first)), int(nthreads), counts_p, totals, err, ERRCAP), err)
+    return take_counts(), totals[:n]
 
 
 def count_combo_barcodes_single_files(paths: Sequence[str], constant: str, strand: int, pool: Sequence[Sequence[str]], mismatches: int,
                                       use_first: bool, nthreads: int = 1, devices=None):
     """scg_count_combo_barcodes_single_files -> list of (indices int32[2, K], freq int32[K], total), one per file."""
     if len(pool) != 2:
-        raise ScgError(_lib.SCG_ERR_INVALID, "currently expecting only 2 variable regions for single-end combinatorial barcodes")
-    L = _lib.load()
-    n = len(paths)
-    idx, freq, ks = _per_file_arrays(n)
-    totals = (C.c_int32 * max(n, 1))()
-    err = errbuf()
-    p0, _k0 = cstr_array(pool[0])
-    p1, _k1 = cstr_array(pool[1])
-    farr, _fk = cstr_array([os.fspath(x) for x in paths])
-    with _devices_env(devices):
-        check(L.scg_count_combo_barcodes_single_files(farr, n, constant.encode(), int(strand), p0, len(pool[0]), p1, len(pool[1]),
-                                                      int(mismatches), int(bool(use_first)), int(nthreads), idx, freq, ks, totals,
-                                                      err, _lib.ERRCAP), err)
-    return [(i2, fr, int(totals[f])) for f, (i2, fr) in enumerate(_take_per_file(L, idx, freq, ks, n))]
-
-
-def _per_file_arrays(n: int):
-    """Caller-allocated arrays of n entries for the per-file malloc'd outputs of a many-files entry (2 x K_f indices, K_f
-    frequencies, K_f)."""
-    return (_lib.i32_p * max(n, 1))(), (_lib.i32_p * max(n, 1))(), (C.c_int64 * max(n, 1))()
-
-
-def _take_per_file(L, idx, freq, ks, n: int):
-    """Those outputs as a list of (indices int32[2, K_f], freq int32[K_f]), released on the C side whatever happens."""
-    out = []
-    try:
-        for f in range(n):
-            K = int(ks[f])
-            i2 = np.ctypeslib.as_array(idx[f], shape=(max(2 * K, 1),))[:2 * K].reshape(K, 2).T.copy() if K else np.zeros((2, 0), dtype=np.int32)
-            fr = np.ctypeslib.as_array(freq[f], shape=(max(K, 1),))[:K].copy() if K else np.zeros(0, dtype=np.int32)
-            out.append((i2.astype(np.int32), fr.astype(np.int32)))
-    finally:
-        for f in range(n):
-            L.scg_free(idx[f])
-            L.scg_free(freq[f])
-    return out
+        raise ScgError(_lib.SCG_ERR_INVALID, TWO_REGIONS)
+    L, err = _lib.load(), errbuf()
+    with _files_call(devices, paths) as (n, (farr,), (totals,)), per_file_combo_outputs(L, n) as (combos, take):
+        check(L.scg_count_combo_barcodes_single_files(farr, n, constant.encode(), int(strand), *_lib.pool(pool[0]), *_lib.pool(pool[1]),
+                                                      int(mismatches), int(bool(use_first)), int(nthreads), *combos, totals, err, ERRCAP), err)
+        return [(idx, freq, total) for (idx, freq), total in zip(take(), totals[:n])]
 
 
 def count_dual_barcodes_files(paths1: Sequence[str], constant1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],
@@ -159,39 +225,16 @@ def count_dual_barcodes_files(paths1: Sequence[str], constant1: str, reverse1: b
                               randomized: bool, use_first: bool, nthreads: int = 1, devices=None):
     """scg_count_dual_barcodes_files -> (counts int32[len(pool1), n_files], totals list)."""
     if len(pool1) != len(pool2):
-        raise ScgError(_lib.SCG_ERR_INVALID, "both barcode pools should be of the same length")
+        raise ScgError(_lib.SCG_ERR_INVALID, SAME_LENGTH)
     if len(paths1) != len(paths2):
         raise ValueError("paths1 and paths2 differ in length")
-    L = _lib.load()
-    n = len(paths1)
-    counts = np.zeros((max(n, 1), max(len(pool1), 1)), dtype=np.int32)
-    totals = (C.c_int32 * max(n, 1))()
-    err = errbuf()
-    a1, _k1 = cstr_array(pool1)
-    a2, _k2 = cstr_array(pool2)
-    f1, _fk1 = cstr_array([os.fspath(x) for x in paths1])
-    f2, _fk2 = cstr_array([os.fspath(x) for x in paths2])
-    with _devices_env(devices):
-        check(L.scg_count_dual_barcodes_files(f1, constant1.encode(), int(bool(reverse1)), int(mismatches1), a1,
-                                              f2, constant2.encode(), int(bool(reverse2)), int(mismatches2), a2, len(pool1), n,
-                                              int(bool(randomized)), int(bool(use_first)), int(nthreads),
-                                              _files_out(counts, len(pool1)), totals, err, _lib.ERRCAP), err)
-    return _files_matrix(counts, len(pool1), n), [int(totals[i]) for i in range(n)]
-
-
-def count_single_barcodes_paired(path1: str, path2: str, constant: str, strand: int, pool: Sequence[str], mismatches: int, use_first: bool,
-                                 nthreads: int = 1):
-    """kaori::SingleBarcodePairedEnd (handlers/SingleBarcodePairedEnd.hpp:93-124) over two files: the barcode of a pair is
-    looked for on either mate -> (counts int32[len(pool)], total pairs)."""
-    L = _lib.load()
-    counts = np.zeros(max(len(pool), 1), dtype=np.int32)
-    total = C.c_int32(0)
-    err = errbuf()
-    parr, _keep = cstr_array(pool)
-    check(L.scg_count_single_barcodes_paired(os.fspath(path1).encode(), os.fspath(path2).encode(), constant.encode(), int(strand), parr,
-                                             len(pool), int(mismatches), int(bool(use_first)), int(nthreads),
-                                             counts.ctypes.data_as(_lib.i32_p), C.byref(total), err, _lib.ERRCAP), err)
-    return counts[:len(pool)].copy(), int(total.value)
+    L, err = _lib.load(), errbuf()
+    counts_p, take_counts = _files_counts(len(pool1), len(paths1))
+    with _files_call(devices, paths1, paths2) as (n, (f1, f2), (totals,)):
+        check(L.scg_count_dual_barcodes_files(f1, constant1.encode(), int(bool(reverse1)), int(mismatches1), cstr_array(pool1)[0],
+                                              f2, constant2.encode(), int(bool(reverse2)), int(mismatches2), cstr_array(pool2)[0], len(pool1), n,
+                                              int(bool(randomized)), int(bool(use_first)), int(nthreads), counts_p, totals, err, ERRCAP), err)
+    return take_counts(), totals[:n]
 
 
 def count_single_barcodes_paired_files(paths1: Sequence[str], paths2: Sequence[str], constant: str, strand: int, pool: Sequence[str],
@@ -199,19 +242,12 @@ def count_single_barcodes_paired_files(paths1: Sequence[str], paths2: Sequence[s
     """scg_count_single_barcodes_paired_files -> (counts int32[len(pool), n_files], totals list)."""
     if len(paths1) != len(paths2):
         raise ValueError("paths1 and paths2 differ in length")
-    L = _lib.load()
-    n = len(paths1)
-    counts = np.zeros((max(n, 1), max(len(pool), 1)), dtype=np.int32)
-    totals = (C.c_int32 * max(n, 1))()
-    err = errbuf()
-    parr, _keep = cstr_array(pool)
-    f1, _fk1 = cstr_array([os.fspath(x) for x in paths1])
-    f2, _fk2 = cstr_array([os.fspath(x) for x in paths2])
-    with _devices_env(devices):
-        check(L.scg_count_single_barcodes_paired_files(f1, f2, n, constant.encode(), int(strand), parr, len(pool), int(mismatches),
-                                                       int(bool(use_first)), int(nthreads), _files_out(counts, len(pool)), totals,
-                                                       err, _lib.ERRCAP), err)
-    return _files_matrix(counts, len(pool), n), [int(totals[i]) for i in range(n)]
+    L, err = _lib.load(), errbuf()
+    counts_p, take_counts = _files_counts(len(pool), len(paths1))
+    with _files_call(devices, paths1, paths2) as (n, (f1, f2), (totals,)):
+        check(L.scg_count_single_barcodes_paired_files(f1, f2, n, constant.encode(), int(strand), *_lib.pool(pool), int(mismatches),
+                                                       int(bool(use_first)), int(nthreads), counts_p, totals, err, ERRCAP), err)
+    return take_counts(), totals[:n]
 
 
 def count_dual_barcodes_diagnostics_files(paths1: Sequence[str], constant1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],
@@ -221,68 +257,44 @@ def count_dual_barcodes_diagnostics_files(paths1: Sequence[str], constant1: str,
     native call -> (counts int32[len(pool1), n_files], list of (indices int32[2, K], freq int32[K]) per file, totals list,
     barcode1_only list, barcode2_only list)."""
     if len(pool1) != len(pool2):
-        raise ScgError(_lib.SCG_ERR_INVALID, "both barcode pools should be of the same length")
+        raise ScgError(_lib.SCG_ERR_INVALID, SAME_LENGTH)
     if len(paths1) != len(paths2):
         raise ValueError("paths1 and paths2 differ in length")
-    L = _lib.load()
-    n = len(paths1)
-    counts = np.zeros((max(n, 1), max(len(pool1), 1)), dtype=np.int32)
-    idx, freq, ks = _per_file_arrays(n)
-    totals, b1, b2 = (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))()
-    err = errbuf()
-    a1, _k1 = cstr_array(pool1)
-    a2, _k2 = cstr_array(pool2)
-    f1, _fk1 = cstr_array([os.fspath(x) for x in paths1])
-    f2, _fk2 = cstr_array([os.fspath(x) for x in paths2])
-    with _devices_env(devices):
-        check(L.scg_count_dual_barcodes_diagnostics_files(f1, constant1.encode(), int(bool(reverse1)), int(mismatches1), a1,
-                                                          f2, constant2.encode(), int(bool(reverse2)), int(mismatches2), a2, len(pool1), n,
-                                                          int(bool(randomized)), int(bool(use_first)), int(nthreads),
-                                                          _files_out(counts, len(pool1)), idx, freq, ks, totals, b1, b2,
-                                                          err, _lib.ERRCAP), err)
-    invalid = _take_per_file(L, idx, freq, ks, n)
-    return (_files_matrix(counts, len(pool1), n), invalid, [int(totals[i]) for i in range(n)],
-            [int(b1[i]) for i in range(n)], [int(b2[i]) for i in range(n)])
+    L, err = _lib.load(), errbuf()
+    counts_p, take_counts = _files_counts(len(pool1), len(paths1))
+    with _files_call(devices, paths1, paths2, scalars=3) as (n, (f1, f2), (totals, b1, b2)), per_file_combo_outputs(L, n) as (combos, take):
+        check(L.scg_count_dual_barcodes_diagnostics_files(f1, constant1.encode(), int(bool(reverse1)), int(mismatches1), cstr_array(pool1)[0],
+                                                          f2, constant2.encode(), int(bool(reverse2)), int(mismatches2), cstr_array(pool2)[0],
+                                                          len(pool1), n, int(bool(randomized)), int(bool(use_first)), int(nthreads),
+                                                          counts_p, *combos, totals, b1, b2, err, ERRCAP), err)
+        return take_counts(), take(), totals[:n], b1[:n], b2[:n]
 
 
 def count_dual_barcodes_single_end_files(paths: Sequence[str], constant: str, pools: Sequence[Sequence[str]], strand: int, mismatches: int,
                                          use_first: bool, nthreads: int = 1, devices=None):
     """scg_count_dual_barcodes_single_end_files: every file of matrixOfDualBarcodesSingleEnd in one native call
     -> (counts int32[n combinations, n_files], totals list)."""
-    L = _lib.load()
-    n = len(paths)
-    nch = len(pools[0]) if pools else 0
-    counts = np.zeros((max(n, 1), max(nch, 1)), dtype=np.int32)
-    totals = (C.c_int32 * max(n, 1))()
-    err = errbuf()
-    rows, sizes, _keep = _lib.cstr_matrix(pools)
-    farr, _fk = cstr_array([os.fspath(x) for x in paths])
-    with _devices_env(devices):
+    L, err = _lib.load(), errbuf()
+    counts_p, take_counts = _files_counts(len(pools[0]) if pools else 0, len(paths))
+    rows, sizes, _keep = cstr_matrix(pools)
+    with _files_call(devices, paths) as (n, (farr,), (totals,)):
         check(L.scg_count_dual_barcodes_single_end_files(farr, n, constant.encode(), rows, sizes, len(pools), int(strand), int(mismatches),
-                                                         int(bool(use_first)), int(nthreads), _files_out(counts, nch), totals,
-                                                         err, _lib.ERRCAP), err)
-    return _files_matrix(counts, nch, n), [int(totals[i]) for i in range(n)]
+                                                         int(bool(use_first)), int(nthreads), counts_p, totals, err, ERRCAP), err)
+    return take_counts(), totals[:n]
 
 
 def count_dual_barcodes_single_end_diagnostics_files(paths: Sequence[str], constant: str, pools: Sequence[Sequence[str]], strand: int,
                                                      mismatches: int, use_first: bool, nthreads: int = 1, devices=None):
     """scg_count_dual_barcodes_single_end_diagnostics_files: matrixOfDualBarcodesSingleEnd(include.invalid=TRUE) in one native
     call -> (counts int32[n combinations, n_files], list of (indices int32[2, K], freq int32[K]) per file, totals list)."""
-    L = _lib.load()
-    n = len(paths)
-    nch = len(pools[0]) if pools else 0
-    counts = np.zeros((max(n, 1), max(nch, 1)), dtype=np.int32)
-    idx, freq, ks = _per_file_arrays(n)
-    totals = (C.c_int32 * max(n, 1))()
-    err = errbuf()
-    rows, sizes, _keep = _lib.cstr_matrix(pools)
-    farr, _fk = cstr_array([os.fspath(x) for x in paths])
-    with _devices_env(devices):
+    L, err = _lib.load(), errbuf()
+    counts_p, take_counts = _files_counts(len(pools[0]) if pools else 0, len(paths))
+    rows, sizes, _keep = cstr_matrix(pools)
+    with _files_call(devices, paths) as (n, (farr,), (totals,)), per_file_combo_outputs(L, n) as (combos, take):
         check(L.scg_count_dual_barcodes_single_end_diagnostics_files(farr, n, constant.encode(), rows, sizes, len(pools), int(strand),
                                                                      int(mismatches), int(bool(use_first)), int(nthreads),
-                                                                     _files_out(counts, nch), idx, freq, ks, totals, err, _lib.ERRCAP), err)
-    invalid = _take_per_file(L, idx, freq, ks, n)
-    return _files_matrix(counts, nch, n), invalid, [int(totals[i]) for i in range(n)]
+                                                                     counts_p, *combos, totals, err, ERRCAP), err)
+        return take_counts(), take(), totals[:n]
 
 
 def count_combo_barcodes_paired_files(paths1: Sequence[str], constant1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],
@@ -292,85 +304,13 @@ def count_combo_barcodes_paired_files(paths1: Sequence[str], constant1: str, rev
     -> list of (indices int32[2, K], freq int32[K], total, barcode1_only, barcode2_only), one per pair of files."""
     if len(paths1) != len(paths2):
         raise ValueError("paths1 and paths2 differ in length")
-    L = _lib.load()
-    n = len(paths1)
-    idx, freq, ks = _per_file_arrays(n)
-    totals, b1, b2 = (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))()
-    err = errbuf()
-    a1, _k1 = cstr_array(pool1)
-    a2, _k2 = cstr_array(pool2)
-    f1, _fk1 = cstr_array([os.fspath(x) for x in paths1])
-    f2, _fk2 = cstr_array([os.fspath(x) for x in paths2])
-    with _devices_env(devices):
-        check(L.scg_count_combo_barcodes_paired_files(f1, constant1.encode(), int(bool(reverse1)), int(mismatches1), a1, len(pool1),
-                                                      f2, constant2.encode(), int(bool(reverse2)), int(mismatches2), a2, len(pool2), n,
+    L, err = _lib.load(), errbuf()
+    with _files_call(devices, paths1, paths2, scalars=3) as (n, (f1, f2), (totals, b1, b2)), per_file_combo_outputs(L, n) as (combos, take):
+        check(L.scg_count_combo_barcodes_paired_files(f1, constant1.encode(), int(bool(reverse1)), int(mismatches1), *_lib.pool(pool1),
+                                                      f2, constant2.encode(), int(bool(reverse2)), int(mismatches2), *_lib.pool(pool2), n,
                                                       int(bool(randomized)), int(bool(use_first)), int(nthreads),
-                                                      idx, freq, ks, totals, b1, b2, err, _lib.ERRCAP), err)
-    return [(i2, fr, int(totals[f]), int(b1[f]), int(b2[f])) for f, (i2, fr) in enumerate(_take_per_file(L, idx, freq, ks, n))]
-
-
-def count_dual_barcodes(path1: str, constant1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],
-                        path2: str, constant2: str, reverse2: bool, mismatches2: int, pool2: Sequence[str],
-                        randomized: bool, use_first: bool, diagnostics: bool = False, nthreads: int = 1):
-    """src/count_dual_barcodes.cpp:74-117 -> (counts int32[n pairs], total), or with diagnostics=True the
-    five outputs of the include.invalid=TRUE branch: (counts, (indices int32[2, K] 0-based, freq), total,
-    barcode1_only, barcode2_only)."""
-    if len(pool1) != len(pool2):
-        # kaori/handlers/DualBarcodesPairedEnd.hpp:106-109
-        raise ScgError(_lib.SCG_ERR_INVALID, "both barcode pools should be of the same length")
-    L = _lib.load()
-    if diagnostics:
-        counts = np.zeros(max(len(pool1), 1), dtype=np.int32)
-        idx_p, freq_p = _lib.i32_p(), _lib.i32_p()
-        k = C.c_int64(0)
-        total, b1, b2 = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-        err = errbuf()
-        p1, _k1 = cstr_array(pool1)
-        p2, _k2 = cstr_array(pool2)
-        check(L.scg_count_dual_barcodes_diagnostics(os.fspath(path1).encode(), constant1.encode(), int(bool(reverse1)), int(mismatches1), p1,
-                                                    os.fspath(path2).encode(), constant2.encode(), int(bool(reverse2)), int(mismatches2), p2,
-                                                    len(pool1), int(bool(randomized)), int(bool(use_first)), int(nthreads),
-                                                    counts.ctypes.data_as(_lib.i32_p), C.byref(idx_p), C.byref(freq_p), C.byref(k),
-                                                    C.byref(total), C.byref(b1), C.byref(b2), err, _lib.ERRCAP), err)
-        K = int(k.value)
-        try:
-            idx = np.ctypeslib.as_array(idx_p, shape=(max(2 * K, 1),))[:2 * K].reshape(K, 2).T.copy()
-            freq = np.ctypeslib.as_array(freq_p, shape=(max(K, 1),))[:K].copy()
-        finally:
-            L.scg_free(idx_p)
-            L.scg_free(freq_p)
-        return counts[:len(pool1)].copy(), (idx.astype(np.int32), freq.astype(np.int32)), int(total.value), int(b1.value), int(b2.value)
-    counts = np.zeros(max(len(pool1), 1), dtype=np.int32)
-    total = C.c_int32(0)
-    err = errbuf()
-    p1, _k1 = cstr_array(pool1)
-    p2, _k2 = cstr_array(pool2)
-    check(L.scg_count_dual_barcodes(os.fspath(path1).encode(), constant1.encode(), int(bool(reverse1)), int(mismatches1), p1,
-                                    os.fspath(path2).encode(), constant2.encode(), int(bool(reverse2)), int(mismatches2), p2,
-                                    len(pool1), int(bool(randomized)), int(bool(use_first)), int(bool(diagnostics)), int(nthreads),
-                                    counts.ctypes.data_as(_lib.i32_p), C.byref(total), err, _lib.ERRCAP), err)
-    return counts[:len(pool1)].copy(), int(total.value)
-
-
-def count_random_barcodes(path: str, constant: str, strand: int, mismatches: int, use_first: bool, nthreads: int = 1):
-    """src/count_random_barcodes.cpp:41-62 -> ((sequences list[str] sorted, freq int32[K]), total)."""
-    L = _lib.load()
-    seq_p = C.c_void_p()
-    freq_p = _lib.i32_p()
-    k, vlen, total = C.c_int64(0), C.c_int32(0), C.c_int32(0)
-    err = errbuf()
-    check(L.scg_count_random_barcodes(os.fspath(path).encode(), constant.encode(), int(strand), int(mismatches), int(bool(use_first)),
-                                      int(nthreads), C.byref(seq_p), C.byref(freq_p), C.byref(k), C.byref(vlen), C.byref(total),
-                                      err, _lib.ERRCAP), err)
-    K, W = int(k.value), int(vlen.value)
-    try:
-        blob = C.string_at(seq_p, K * (W + 1)) if K else b""
-        seqs = [blob[i * (W + 1): i * (W + 1) + W].decode("latin-1") for i in range(K)]
-        freq = np.ctypeslib.as_array(freq_p, shape=(max(K, 1),))[:K].copy().astype(np.int32)
-    finally:
-        L.scg_free(seq_p)
-        L.scg_free(freq_p)
-    return (seqs, freq), int(total.value)
+                                                      *combos, totals, b1, b2, err, ERRCAP), err)
+        return [(idx, freq, *scalars) for (idx, freq), *scalars in zip(take(), totals[:n], b1[:n], b2[:n])]
 
 
 def count_random_barcodes_files(paths: Sequence[str], constant: str, strand: int, mismatches: int, use_first: bool, nthreads: int = 1,
@@ -378,94 +318,31 @@ def count_random_barcodes_files(paths: Sequence[str], constant: str, strand: int
     """scg_count_random_barcodes_files: every file of matrixOfRandomBarcodes in one native call, tallied in HBM
     -> (keys list[str] sorted: the union over the files, matrix int32[K, n_files] dense as R builds it
     (R/countRandomBarcodes.R:87-92), totals int32[n_files])."""
-    L = _lib.load()
-    n = len(paths)
-    seq_p = C.c_void_p()
-    colptr_p, rows_p, freq_p = _lib.i64_p(), _lib.i32_p(), _lib.i32_p()
+    L, err = _lib.load(), errbuf()
+    seq_p, colptr_p, rows_p, freq_p = C.c_void_p(), _lib.i64_p(), i32_p(), i32_p()
     k, vlen = C.c_int64(0), C.c_int32(0)
-    totals = np.zeros(max(n, 1), dtype=np.int32)
-    err = errbuf()
-    farr, _fk = cstr_array([os.fspath(x) for x in paths])
-    with _devices_env(devices):
+    with _files_call(devices, paths) as (n, (farr,), (totals,)):
         check(L.scg_count_random_barcodes_files(farr, n, constant.encode(), int(strand), int(mismatches), int(bool(use_first)), int(nthreads),
                                                 C.byref(seq_p), C.byref(k), C.byref(vlen), C.byref(colptr_p), C.byref(rows_p), C.byref(freq_p),
-                                                totals.ctypes.data_as(_lib.i32_p), err, _lib.ERRCAP), err)
-    K, W = int(k.value), int(vlen.value)
+                                                totals, err, ERRCAP), err)
+    K = int(k.value)
     try:
-        blob = C.string_at(seq_p, K * (W + 1)) if K else b""
-        keys = [blob[i * (W + 1): i * (W + 1) + W].decode("latin-1") for i in range(K)]
+        keys = _lib.decode_sequences(seq_p, K, int(vlen.value))
         colptr = np.ctypeslib.as_array(colptr_p, shape=(n + 1,)).copy()
         nnz = int(colptr[n])
         rows = np.ctypeslib.as_array(rows_p, shape=(max(nnz, 1),))[:nnz].copy()
         freq = np.ctypeslib.as_array(freq_p, shape=(max(nnz, 1),))[:nnz].copy()
     finally:
-        L.scg_free(seq_p)
-        L.scg_free(colptr_p)
-        L.scg_free(rows_p)
-        L.scg_free(freq_p)
+        for p in (seq_p, colptr_p, rows_p, freq_p):
+            L.scg_free(p)
     matrix = np.zeros((K, n), dtype=np.int32)
     matrix[rows, np.repeat(np.arange(n), np.diff(colptr))] = freq
-    return keys, matrix, totals[:n].copy()
+    return keys, matrix, np.array(totals[:n], dtype=np.int32)
 
 
-def count_dual_barcodes_single_end(path: str, constant: str, pools: Sequence[Sequence[str]], strand: int, mismatches: int,
-                                   use_first: bool, diagnostics: bool = False, nthreads: int = 1):
-    """src/count_dual_barcodes_single_end.cpp:53-87 -> (counts int32[n combinations], total), or with diagnostics=True
-    (counts, (indices int32[2, K] 0-based, freq), total) as in its include.invalid=TRUE branch."""
-    L = _lib.load()
-    nch = len(pools[0]) if pools else 0
-    counts = np.zeros(max(nch, 1), dtype=np.int32)
-    total = C.c_int32(0)
-    err = errbuf()
-    rows, sizes, _keep = _lib.cstr_matrix(pools)
-    if diagnostics:
-        idx_p, freq_p = _lib.i32_p(), _lib.i32_p()
-        k = C.c_int64(0)
-        check(L.scg_count_dual_barcodes_single_end_diagnostics(os.fspath(path).encode(), constant.encode(), rows, sizes, len(pools),
-                                                               int(strand), int(mismatches), int(bool(use_first)), int(nthreads),
-                                                               counts.ctypes.data_as(_lib.i32_p), C.byref(idx_p), C.byref(freq_p), C.byref(k),
-                                                               C.byref(total), err, _lib.ERRCAP), err)
-        K = int(k.value)
-        try:
-            idx = np.ctypeslib.as_array(idx_p, shape=(max(2 * K, 1),))[:2 * K].reshape(K, 2).T.copy()
-            freq = np.ctypeslib.as_array(freq_p, shape=(max(K, 1),))[:K].copy()
-        finally:
-            L.scg_free(idx_p)
-            L.scg_free(freq_p)
-        return counts[:nch].copy(), (idx.astype(np.int32), freq.astype(np.int32)), int(total.value)
-    check(L.scg_count_dual_barcodes_single_end(os.fspath(path).encode(), constant.encode(), rows, sizes, len(pools),
-                                               int(strand), int(mismatches), int(bool(use_first)), int(bool(diagnostics)), int(nthreads),
-                                               counts.ctypes.data_as(_lib.i32_p), C.byref(total), err, _lib.ERRCAP), err)
-    return counts[:nch].copy(), int(total.value)
-
-
-def count_combo_barcodes_paired(path1: str, constant1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],
-                                path2: str, constant2: str, reverse2: bool, mismatches2: int, pool2: Sequence[str],
-                                randomized: bool, use_first: bool, nthreads: int = 1):
-    """src/count_combo_barcodes_paired.cpp:57-95 -> (indices int32[2, K] 0-based sorted by (first, second),
-    freq int32[K], total, barcode1_only, barcode2_only)."""
-    L = _lib.load()
-    idx_p, freq_p = _lib.i32_p(), _lib.i32_p()
-    k = C.c_int64(0)
-    total, b1, b2 = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-    err = errbuf()
-    p1, _k1 = cstr_array(pool1)
-    p2, _k2 = cstr_array(pool2)
-    check(L.scg_count_combo_barcodes_paired(os.fspath(path1).encode(), constant1.encode(), int(bool(reverse1)), int(mismatches1), p1, len(pool1),
-                                            os.fspath(path2).encode(), constant2.encode(), int(bool(reverse2)), int(mismatches2), p2, len(pool2),
-                                            int(bool(randomized)), int(bool(use_first)), int(nthreads),
-                                            C.byref(idx_p), C.byref(freq_p), C.byref(k),
-                                            C.byref(total), C.byref(b1), C.byref(b2), err, _lib.ERRCAP), err)
-    K = int(k.value)
-    try:
-        idx = np.ctypeslib.as_array(idx_p, shape=(max(2 * K, 1),))[:2 * K].reshape(K, 2).T.copy()
-        freq = np.ctypeslib.as_array(freq_p, shape=(max(K, 1),))[:K].copy()
-    finally:
-        L.scg_free(idx_p)
-        L.scg_free(freq_p)
-    return idx.astype(np.int32), freq.astype(np.int32), int(total.value), int(b1.value), int(b2.value)
-
-
+# =============================================================================================
+# Per-read assignment, match_barcodes, parse_fastq
+# =============================================================================================
 def assign_single_barcodes(path: str, template: str, strand: int, pool: Sequence[str], mismatches: int = 0, use_first: bool = True,
                            batch_reads: int = 1 << 22, device: int = -1):
     """What every read of a FASTQ file matched: kaori::SimpleSingleMatch::State per read (SimpleSingleMatch.hpp:103-140) as
@@ -491,26 +368,18 @@ def assign_single_barcodes(path: str, template: str, strand: int, pool: Sequence
 
 def match_barcodes(sequences: Sequence[str], choices: Sequence[str], substitutions: int = 0, reverse: bool = False):
     """src/match_barcodes.cpp:6-37 -> (index int32[n] 0-based with -1 for NA, mismatches int32[n] with -1 for NA)."""
-    L = _lib.load()
+    L, err = _lib.load(), errbuf()
     n = len(sequences)
-    idx = np.zeros(max(n, 1), dtype=np.int32)
-    mm = np.zeros(max(n, 1), dtype=np.int32)
-    err = errbuf()
-    sa, _k = cstr_array(sequences)
-    ca, _k2 = cstr_array(choices)
-    check(L.scg_match_barcodes(sa, n, ca, len(choices), int(substitutions), int(bool(reverse)),
-                               idx.ctypes.data_as(_lib.i32_p), mm.ctypes.data_as(_lib.i32_p), err, _lib.ERRCAP), err)
+    (idx, idx_p), (mm, mm_p) = _int32_out(n), _int32_out(n)
+    check(L.scg_match_barcodes(*_lib.pool(sequences), *_lib.pool(choices), int(substitutions), int(bool(reverse)), idx_p, mm_p, err, ERRCAP), err)
     return idx[:n].copy(), mm[:n].copy()
 
 
 def parse_fastq(path: str):
     """kaori/FastqReader.hpp:42-110 -> (uint8 sequence bytes, uint64 offsets[n + 1])."""
-    L = _lib.load()
-    seqs_p = C.c_void_p()
-    offs_p = C.c_void_p()
-    n = C.c_int64(0)
-    err = errbuf()
-    check(L.scg_parse_fastq(os.fspath(path).encode(), C.byref(seqs_p), C.byref(offs_p), C.byref(n), err, _lib.ERRCAP), err)
+    L, err = _lib.load(), errbuf()
+    seqs_p, offs_p, n = C.c_void_p(), C.c_void_p(), C.c_int64(0)
+    check(L.scg_parse_fastq(_path(path), C.byref(seqs_p), C.byref(offs_p), C.byref(n), err, ERRCAP), err)
     try:
         offs = np.ctypeslib.as_array(C.cast(offs_p, C.POINTER(C.c_uint64)), shape=(n.value + 1,)).copy()
         nb = int(offs[-1])

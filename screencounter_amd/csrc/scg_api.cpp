@@ -22,6 +22,78 @@ int new_plan(scg_plan** plan_out, int device, char* err, size_t errcap, const Co
     });
 }
 
+// ---- many files on one compiled plan per device (matrixOf*) ------------------------------------------------------------
+// What the nine many-files entries share, after the null-argument condition each states for itself.  An entry is: its
+// lists of paths, the order of its first steps, what it compiles, and how a counted file is read out.
+
+// One list of n_files paths (single-end), or two (paired: paths2 is not null).
+struct FileLists { const char* const* paths1; const char* const* paths2; int32_t n_files; };
+
+// The order of the first steps, which is the order of the entry's errors (include/scg.h, "Many files in one call").
+enum class Order {
+    ARGUMENTS_FIRST,        // compile, device list: argument errors before any file is opened or any device is touched
+    FILE0_FIRST,            // reader(s) of file 0, device list, compile: a missing first file first, as in a loop over files
+    FILE0_THEN_ARGUMENTS,   // reader of file 0, compile, device list (the random entry)
+};
+
+typedef std::function<void(scg_plan*, int32_t)> ReadFile;     // (the plan that counted file f, f) -> file f's outputs
+
+// Null paths, no files (nothing is written; null), then the first steps in `order`, one plan per device, and every file
+// counted by schedule_single_end / schedule_paired and read by `read_file`.  The plans are handed back for a read-out
+// that needs them all (the random entry).
+std::unique_ptr<PlanSet> count_files(const FileLists& files, int nthreads, Order order, const Compile& compile, const ReadFile& read_file) {
+    const int32_t n = files.n_files;
+    for (int32_t f = 0; f < n; ++f) if (!files.paths1[f] || (files.paths2 && !files.paths2[f])) throw Error(SCG_ERR_INVALID, "null argument");
+    if (n == 0) return nullptr;
+    if (order != Order::ARGUMENTS_FIRST) {
+        scg::FastqStream probe1(files.paths1[0]);
+        if (files.paths2) scg::FastqStream probe2(files.paths2[0]);
+    }
+    std::unique_ptr<PlanSet> set;
+    if (order == Order::FILE0_FIRST) {
+        const std::vector<int> devices = devices_for_files(n);
+        set.reset(new PlanSet(compile(), devices));
+    } else {
+        std::unique_ptr<scg_plan> compiled = compile();
+        set.reset(new PlanSet(std::move(compiled), devices_for_files(n)));
+    }
+    if (files.paths2) schedule_paired(n, *set, files.paths1, files.paths2, nthreads, read_file);
+    else schedule_single_end(n, *set, files.paths1, nthreads, read_file);
+    return set;
+}
+
+// The outputs of a many-files entry with a library, in the order of its prototype: caller-allocated arrays of n_files
+// entries (null: the entry has no such output); `counts` is column-major, one column of n_pool[0] counts per file.
+struct PerFile {
+    int32_t* counts;
+    int32_t** idx; int32_t** freq; int64_t* k;
+    int32_t* totals; int32_t* b1; int32_t* b2;
+};
+enum class ReadOut { COUNTS, COMBINATIONS, DIAGNOSTICS };
+
+// File f into entry f of those arrays, by the function the one-file entry reads its outputs with.  Column f starts at
+// n_pool[0] * f, the plan's own pool count: the n_pool argument where the entry has one (compile_* store it), and all
+// there is for the single-end dual entries.
+void read_file_into(const PerFile& out, ReadOut what, scg_plan* P, int32_t f) {
+    const std::vector<scg_plan*> plan(1, P);
+    int32_t* column = out.counts ? out.counts + static_cast<size_t>(P->n_pool[0]) * static_cast<size_t>(f) : nullptr;
+    switch (what) {
+    case ReadOut::COUNTS: result_counts(plan, column, &out.totals[f]); break;
+    case ReadOut::COMBINATIONS: result_combinations(plan, &out.idx[f], &out.freq[f], &out.k[f], &out.totals[f]); break;
+    case ReadOut::DIAGNOSTICS:
+        result_diagnostics(plan, column, &out.idx[f], &out.freq[f], &out.k[f], &out.totals[f], out.b1 ? &out.b1[f] : nullptr, out.b2 ? &out.b2[f] : nullptr);
+        break;
+    }
+}
+
+// count_files for the eight entries with a library.  Per-file pointer outputs are all-NULL (k: 0) before anything else
+// happens -- the null paths included -- and again after any failure (with_per_file_outputs).
+void count_files_into(const FileLists& files, int nthreads, Order order, const Compile& compile, ReadOut what, const PerFile& out) {
+    auto run = [&] { count_files(files, nthreads, order, compile, [&](scg_plan* P, int32_t f) { read_file_into(out, what, P, f); }); };
+    if (out.idx) with_per_file_outputs(out.idx, out.freq, out.k, files.n_files, run);
+    else run();
+}
+
 } // namespace
 
 // -------------------------------------------------------------------------------------------------
@@ -553,21 +625,15 @@ int scg_count_single_barcodes_files(const char* const* paths, int32_t n_files, c
                                     int32_t* counts_out, int32_t* totals_out, char* err, size_t errcap) {
     return guarded(err, errcap, [&] {
         if (n_files < 0 || (n_files > 0 && (!paths || !totals_out || (n_pool > 0 && !counts_out)))) throw Error(SCG_ERR_INVALID, "null argument");
-        for (int32_t f = 0; f < n_files; ++f) if (!paths[f]) throw Error(SCG_ERR_INVALID, "null argument");
-        if (n_files == 0) return;
-        if (n_files == 1) {      // one file: all devices share it
+        if (n_files == 1) {      // one file: all devices share it (a null path is the one-file entry's "null argument" too)
             const int rc = scg_count_single_barcodes(paths[0], constant, strand, pool, n_pool, mismatches, use_first, nthreads,
                                                      counts_out, totals_out, err, errcap);
             if (rc != SCG_OK) throw Error(rc, err ? err : "");
             return;
         }
-        scg::FastqStream probe(paths[0]);                          // the first file's reader comes before the argument checks, as in a loop over files
-        const std::vector<int> devices = devices_for_files(n_files);
-        PlanSet set(compile_single(constant, strand, pool, n_pool, mismatches, use_first), devices);
-        const size_t stride = static_cast<size_t>(n_pool);
-        schedule_single_end(n_files, set, paths, nthreads, [&](scg_plan* P, int32_t f) {
-            result_counts(std::vector<scg_plan*>(1, P), counts_out + stride * static_cast<size_t>(f), &totals_out[f]);
-        });
+        count_files_into(FileLists{paths, nullptr, n_files}, nthreads, Order::FILE0_FIRST, [&] {
+            return compile_single(constant, strand, pool, n_pool, mismatches, use_first);
+        }, ReadOut::COUNTS, PerFile{counts_out, nullptr, nullptr, nullptr, totals_out, nullptr, nullptr});
     });
 }
 
@@ -578,16 +644,9 @@ int scg_count_combo_barcodes_single_files(const char* const* paths, int32_t n_fi
                                           char* err, size_t errcap) {
     return guarded(err, errcap, [&] {
         if (n_files < 0 || (n_files > 0 && (!paths || !indices_out || !freq_out || !k_out || !totals_out))) throw Error(SCG_ERR_INVALID, "null argument");
-        with_per_file_outputs(indices_out, freq_out, k_out, n_files, [&] {
-            for (int32_t f = 0; f < n_files; ++f) if (!paths[f]) throw Error(SCG_ERR_INVALID, "null argument");
-            if (n_files == 0) return;
-            scg::FastqStream probe(paths[0]);
-            const std::vector<int> devices = devices_for_files(n_files);
-            PlanSet set(compile_combo(constant, strand, pool0, n_pool0, pool1, n_pool1, mismatches, use_first), devices);
-            schedule_single_end(n_files, set, paths, nthreads, [&](scg_plan* P, int32_t f) {
-                result_combinations(std::vector<scg_plan*>(1, P), &indices_out[f], &freq_out[f], &k_out[f], &totals_out[f]);
-            });
-        });
+        count_files_into(FileLists{paths, nullptr, n_files}, nthreads, Order::FILE0_FIRST, [&] {
+            return compile_combo(constant, strand, pool0, n_pool0, pool1, n_pool1, mismatches, use_first);
+        }, ReadOut::COMBINATIONS, PerFile{nullptr, indices_out, freq_out, k_out, totals_out, nullptr, nullptr});
     });
 }
 
@@ -597,23 +656,17 @@ int scg_count_dual_barcodes_files(const char* const* paths1, const char* constan
                                   int32_t* counts_out, int32_t* totals_out, char* err, size_t errcap) {
     return guarded(err, errcap, [&] {
         if (n_files < 0 || (n_files > 0 && (!paths1 || !paths2 || !totals_out || (n_pool > 0 && !counts_out)))) throw Error(SCG_ERR_INVALID, "null argument");
-        for (int32_t f = 0; f < n_files; ++f) if (!paths1[f] || !paths2[f]) throw Error(SCG_ERR_INVALID, "null argument");
-        if (n_files == 0) return;
-        { scg::FastqStream probe1(paths1[0]); scg::FastqStream probe2(paths2[0]); }
-        const std::vector<int> devices = devices_for_files(n_files);
-        PlanSet set(compile_dual(constant1, reverse1, mismatches1, pool1, constant2, reverse2, mismatches2, pool2, n_pool, randomized, use_first), devices);
-        const size_t stride = static_cast<size_t>(n_pool);
-        schedule_paired(n_files, set, paths1, paths2, nthreads, [&](scg_plan* P, int32_t f) {
-            result_counts(std::vector<scg_plan*>(1, P), counts_out + stride * static_cast<size_t>(f), &totals_out[f]);
-        });
+        count_files_into(FileLists{paths1, paths2, n_files}, nthreads, Order::FILE0_FIRST, [&] {
+            return compile_dual(constant1, reverse1, mismatches1, pool1, constant2, reverse2, mismatches2, pool2, n_pool, randomized, use_first);
+        }, ReadOut::COUNTS, PerFile{counts_out, nullptr, nullptr, nullptr, totals_out, nullptr, nullptr});
     });
 }
 
 // The five entries below check their arguments -- the template and the pools are compiled, host work only -- before any
-// file is opened and any device is touched; then every device gets its plan and takes the files one at a time.  In all
-// eight many-files entries with a library a plan starts every file from reset_plan (counters, sparse combinations, runs in
-// flight, the oversize-read flag), and a file's outputs are read by the function its one-file entry reads them with
-// (result_counts, result_combinations, result_diagnostics).
+// file is opened and any device is touched (Order::ARGUMENTS_FIRST); then every device gets its plan and takes the files
+// one at a time.  In all eight many-files entries with a library a plan starts every file from reset_plan (counters,
+// sparse combinations, runs in flight, the oversize-read flag), and a file's outputs are read by the function its
+// one-file entry reads them with (read_file_into: result_counts, result_combinations, result_diagnostics).
 
 int scg_count_dual_barcodes_diagnostics_files(const char* const* paths1, const char* constant1, int reverse1, int mismatches1, const char* const* pool1,
                                               const char* const* paths2, const char* constant2, int reverse2, int mismatches2, const char* const* pool2,
@@ -626,17 +679,9 @@ int scg_count_dual_barcodes_diagnostics_files(const char* const* paths1, const c
                                             !barcode1_only_out || !barcode2_only_out || (n_pool > 0 && !counts_out)))) {
             throw Error(SCG_ERR_INVALID, "null argument");
         }
-        with_per_file_outputs(invalid_indices_out, invalid_freq_out, k_out, n_files, [&] {
-            for (int32_t f = 0; f < n_files; ++f) if (!paths1[f] || !paths2[f]) throw Error(SCG_ERR_INVALID, "null argument");
-            if (n_files == 0) return;
-            auto compiled = compile_dual(constant1, reverse1, mismatches1, pool1, constant2, reverse2, mismatches2, pool2, n_pool, randomized, use_first, 1);
-            PlanSet set(std::move(compiled), devices_for_files(n_files));
-            const size_t stride = static_cast<size_t>(n_pool);
-            schedule_paired(n_files, set, paths1, paths2, nthreads, [&](scg_plan* P, int32_t f) {
-                result_diagnostics(std::vector<scg_plan*>(1, P), counts_out + stride * static_cast<size_t>(f), &invalid_indices_out[f], &invalid_freq_out[f],
-                                   &k_out[f], &totals_out[f], &barcode1_only_out[f], &barcode2_only_out[f]);
-            });
-        });
+        count_files_into(FileLists{paths1, paths2, n_files}, nthreads, Order::ARGUMENTS_FIRST, [&] {
+            return compile_dual(constant1, reverse1, mismatches1, pool1, constant2, reverse2, mismatches2, pool2, n_pool, randomized, use_first, 1);
+        }, ReadOut::DIAGNOSTICS, PerFile{counts_out, invalid_indices_out, invalid_freq_out, k_out, totals_out, barcode1_only_out, barcode2_only_out});
     });
 }
 
@@ -645,14 +690,9 @@ int scg_count_single_barcodes_paired_files(const char* const* paths1, const char
                                            int32_t* counts_out, int32_t* totals_out, char* err, size_t errcap) {
     return guarded(err, errcap, [&] {
         if (n_files < 0 || (n_files > 0 && (!paths1 || !paths2 || !totals_out || (n_pool > 0 && !counts_out)))) throw Error(SCG_ERR_INVALID, "null argument");
-        for (int32_t f = 0; f < n_files; ++f) if (!paths1[f] || !paths2[f]) throw Error(SCG_ERR_INVALID, "null argument");
-        if (n_files == 0) return;
-        auto compiled = compile_single_paired(constant, strand, pool, n_pool, mismatches, use_first);
-        PlanSet set(std::move(compiled), devices_for_files(n_files));
-        const size_t stride = static_cast<size_t>(n_pool);
-        schedule_paired(n_files, set, paths1, paths2, nthreads, [&](scg_plan* P, int32_t f) {
-            result_counts(std::vector<scg_plan*>(1, P), counts_out + stride * static_cast<size_t>(f), &totals_out[f]);
-        });
+        count_files_into(FileLists{paths1, paths2, n_files}, nthreads, Order::ARGUMENTS_FIRST, [&] {
+            return compile_single_paired(constant, strand, pool, n_pool, mismatches, use_first);
+        }, ReadOut::COUNTS, PerFile{counts_out, nullptr, nullptr, nullptr, totals_out, nullptr, nullptr});
     });
 }
 
@@ -664,14 +704,9 @@ int scg_count_dual_barcodes_single_end_files(const char* const* paths, int32_t n
         if (n_files < 0 || (n_files > 0 && (!paths || !totals_out || (n_regions > 0 && n_pools && n_pools[0] > 0 && !counts_out)))) {
             throw Error(SCG_ERR_INVALID, "null argument");
         }
-        for (int32_t f = 0; f < n_files; ++f) if (!paths[f]) throw Error(SCG_ERR_INVALID, "null argument");
-        if (n_files == 0) return;
-        auto compiled = compile_dual_single_end(constant, strand, pools, n_pools, n_regions, mismatches, use_first);
-        PlanSet set(std::move(compiled), devices_for_files(n_files));
-        const size_t stride = static_cast<size_t>(set.first()->n_pool[0]);
-        schedule_single_end(n_files, set, paths, nthreads, [&](scg_plan* P, int32_t f) {
-            result_counts(std::vector<scg_plan*>(1, P), counts_out + stride * static_cast<size_t>(f), &totals_out[f]);
-        });
+        count_files_into(FileLists{paths, nullptr, n_files}, nthreads, Order::ARGUMENTS_FIRST, [&] {
+            return compile_dual_single_end(constant, strand, pools, n_pools, n_regions, mismatches, use_first);
+        }, ReadOut::COUNTS, PerFile{counts_out, nullptr, nullptr, nullptr, totals_out, nullptr, nullptr});
     });
 }
 
@@ -685,17 +720,9 @@ int scg_count_dual_barcodes_single_end_diagnostics_files(const char* const* path
                                             (n_regions > 0 && n_pools && n_pools[0] > 0 && !counts_out)))) {
             throw Error(SCG_ERR_INVALID, "null argument");
         }
-        with_per_file_outputs(invalid_indices_out, invalid_freq_out, k_out, n_files, [&] {
-            for (int32_t f = 0; f < n_files; ++f) if (!paths[f]) throw Error(SCG_ERR_INVALID, "null argument");
-            if (n_files == 0) return;
-            auto compiled = compile_dual_single_end_diag(constant, strand, pools, n_pools, n_regions, mismatches, use_first);
-            PlanSet set(std::move(compiled), devices_for_files(n_files));
-            const size_t stride = static_cast<size_t>(set.first()->n_pool[0]);
-            schedule_single_end(n_files, set, paths, nthreads, [&](scg_plan* P, int32_t f) {
-                result_diagnostics(std::vector<scg_plan*>(1, P), counts_out + stride * static_cast<size_t>(f), &invalid_indices_out[f], &invalid_freq_out[f],
-                                   &k_out[f], &totals_out[f], nullptr, nullptr);
-            });
-        });
+        count_files_into(FileLists{paths, nullptr, n_files}, nthreads, Order::ARGUMENTS_FIRST, [&] {
+            return compile_dual_single_end_diag(constant, strand, pools, n_pools, n_regions, mismatches, use_first);
+        }, ReadOut::DIAGNOSTICS, PerFile{counts_out, invalid_indices_out, invalid_freq_out, k_out, totals_out, nullptr, nullptr});
     });
 }
 
@@ -712,17 +739,10 @@ int scg_count_combo_barcodes_paired_files(const char* const* paths1, const char*
                                             !barcode1_only_out || !barcode2_only_out))) {
             throw Error(SCG_ERR_INVALID, "null argument");
         }
-        with_per_file_outputs(indices_out, freq_out, k_out, n_files, [&] {
-            for (int32_t f = 0; f < n_files; ++f) if (!paths1[f] || !paths2[f]) throw Error(SCG_ERR_INVALID, "null argument");
-            if (n_files == 0) return;
-            auto compiled = compile_paired_combo(constant1, reverse1, mismatches1, pool1, n_pool1, constant2, reverse2, mismatches2, pool2, n_pool2,
-                                                 randomized, use_first);
-            PlanSet set(std::move(compiled), devices_for_files(n_files));
-            schedule_paired(n_files, set, paths1, paths2, nthreads, [&](scg_plan* P, int32_t f) {
-                result_diagnostics(std::vector<scg_plan*>(1, P), nullptr, &indices_out[f], &freq_out[f], &k_out[f], &totals_out[f],
-                                   &barcode1_only_out[f], &barcode2_only_out[f]);
-            });
-        });
+        count_files_into(FileLists{paths1, paths2, n_files}, nthreads, Order::ARGUMENTS_FIRST, [&] {
+            return compile_paired_combo(constant1, reverse1, mismatches1, pool1, n_pool1, constant2, reverse2, mismatches2, pool2, n_pool2,
+                                        randomized, use_first);
+        }, ReadOut::DIAGNOSTICS, PerFile{nullptr, indices_out, freq_out, k_out, totals_out, barcode1_only_out, barcode2_only_out});
     });
 }
 
@@ -739,7 +759,6 @@ int scg_count_random_barcodes_files(const char* const* paths, int32_t n_files, c
             throw Error(SCG_ERR_INVALID, "null argument");
         }
         *sequences_out = nullptr; *col_ptr_out = nullptr; *rows_out = nullptr; *freq_out = nullptr; *k_out = 0; *length_out = 0;
-        for (int32_t f = 0; f < n_files; ++f) if (!paths[f]) throw Error(SCG_ERR_INVALID, "null argument");
         if (n_files == 0) {                                            // an empty matrix, with arrays to release like any other
             OutPair<char, int64_t> head(1, 1);
             OutPair<int32_t, int32_t> body(1, 1);
@@ -748,18 +767,22 @@ int scg_count_random_barcodes_files(const char* const* paths, int32_t n_files, c
             body.release(rows_out, freq_out);
             return;
         }
-        { scg::FastqStream probe(paths[0]); }                          // the first file's reader comes before the argument checks, as in a loop over files
-        std::unique_ptr<scg_plan> compiled = compile_random(constant, strand, mismatches, use_first);
-        compiled->rnd->files = true;
-        PlanSet set(std::move(compiled), devices_for_files(n_files));
-        std::vector<int> plan_of(static_cast<size_t>(n_files), 0);
+        std::vector<scg_plan*> counted_by(static_cast<size_t>(n_files), nullptr);
         std::vector<std::vector<int32_t> > pairs(static_cast<size_t>(n_files));
-        schedule_single_end(n_files, set, paths, nthreads, [&](scg_plan* P, int32_t f) {
+        const std::unique_ptr<PlanSet> set = count_files(FileLists{paths, nullptr, n_files}, nthreads, Order::FILE0_THEN_ARGUMENTS, [&] {
+            std::unique_ptr<scg_plan> compiled = compile_random(constant, strand, mismatches, use_first);
+            compiled->rnd->files = true;
+            return compiled;
+        }, [&](scg_plan* P, int32_t f) {
             random_harvest(P, pairs[static_cast<size_t>(f)]);
             totals_out[f] = narrow_total(P->total);
-            for (size_t p = 0; p < set.plans.size(); ++p) if (set.plans[p].get() == P) plan_of[static_cast<size_t>(f)] = static_cast<int>(p);
+            counted_by[static_cast<size_t>(f)] = P;
         });
-        result_random_matrix(set, plan_of, pairs, sequences_out, k_out, length_out, col_ptr_out, rows_out, freq_out);
+        std::vector<int> plan_of(static_cast<size_t>(n_files), 0);
+        for (size_t f = 0; f < plan_of.size(); ++f) {
+            for (size_t p = 0; p < set->plans.size(); ++p) if (set->plans[p].get() == counted_by[f]) plan_of[f] = static_cast<int>(p);
+        }
+        result_random_matrix(*set, plan_of, pairs, sequences_out, k_out, length_out, col_ptr_out, rows_out, freq_out);
     });
 }
 

@@ -18,7 +18,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import ScgError, check, cstr_array, errbuf
+from ._lib import ScgError, check, combo_outputs, cstr_array, errbuf
 
 STRANDS = {"original": 0, "reverse": 1, "both": 2}
 
@@ -61,6 +61,29 @@ def _check_offsets(t, name):
         raise ValueError(f"{name} must be a contiguous int32/uint32 CUDA tensor of n_reads + 1 byte offsets")
 
 
+# The batch arguments of one mate (count, assign; count_paired per mate): how many reads, and the max_len hint.
+def _batch_reads(seqs, offsets, fixed_len: int, n: Optional[int] = None) -> int:
+    """Reads in a batch given by offsets or by a fixed length; `n` is the caller's own number, checked against a
+    fixed-length batch."""
+    if offsets is not None:
+        return offsets.numel() - 1 if n is None else n
+    if fixed_len <= 0:
+        raise ValueError("either offsets or a positive fixed_len is required")
+    if n is None:
+        return seqs.numel() // fixed_len
+    if n * fixed_len > seqs.numel():
+        raise ValueError("seqs is shorter than n_reads * fixed_len")
+    return n
+
+
+def _batch_max_len(offsets, fixed_len: int, n: int, max_len: int) -> int:
+    """The caller's hint if there is one; else the fixed length (which the C side uses for such a batch whatever is passed),
+    or for a ragged batch the device reduction of _max_len -- the only step here that synchronises."""
+    if max_len > 0 or n <= 0:
+        return max_len
+    return fixed_len if offsets is None else _max_len(offsets, n)
+
+
 class Plan:
     """A compiled (template, barcode library, options) bound to one GPU."""
 
@@ -75,39 +98,30 @@ class Plan:
 
     # ---- construction -------------------------------------------------------------------------
     @classmethod
+    def _new(cls, symbol: str, args, kind: str, n_pool: Sequence[int], device: int) -> "Plan":
+        """What the factories share: <symbol>(&handle, *args, device, err, errcap) -> Plan."""
+        L, h, err = _lib.load(), C.c_void_p(), errbuf()
+        check(getattr(L, symbol)(C.byref(h), *args, int(device), err, _lib.ERRCAP), err)
+        return cls(h.value, kind, n_pool, device)
+
+    @classmethod
     def single(cls, template: str, strand: int, pool: Sequence[str], mismatches: int = 0, use_first: bool = True,
                device: int = -1) -> "Plan":
-        L = _lib.load()
-        h = C.c_void_p()
-        err = errbuf()
-        parr, _keep = cstr_array(pool)
-        check(L.scg_plan_single(C.byref(h), template.encode(), int(strand), parr, len(pool), int(mismatches),
-                                int(bool(use_first)), int(device), err, _lib.ERRCAP), err)
-        return cls(h.value, "single", (len(pool),), device)
+        return cls._new("scg_plan_single", (template.encode(), int(strand), *_lib.pool(pool), int(mismatches), int(bool(use_first))),
+                        "single", (len(pool),), device)
 
     @classmethod
     def single_paired(cls, template: str, strand: int, pool: Sequence[str], mismatches: int = 0, use_first: bool = True,
                       device: int = -1) -> "Plan":
         """One barcode on either mate of a pair (kaori::SingleBarcodePairedEnd): counted with count_paired(), read with read()."""
-        L = _lib.load()
-        h = C.c_void_p()
-        err = errbuf()
-        parr, _keep = cstr_array(pool)
-        check(L.scg_plan_single_paired(C.byref(h), template.encode(), int(strand), parr, len(pool), int(mismatches),
-                                       int(bool(use_first)), int(device), err, _lib.ERRCAP), err)
-        return cls(h.value, "single_paired", (len(pool),), device)
+        return cls._new("scg_plan_single_paired", (template.encode(), int(strand), *_lib.pool(pool), int(mismatches), int(bool(use_first))),
+                        "single_paired", (len(pool),), device)
 
     @classmethod
     def combo(cls, template: str, strand: int, pool0: Sequence[str], pool1: Sequence[str], mismatches: int = 0,
               use_first: bool = True, device: int = -1) -> "Plan":
-        L = _lib.load()
-        h = C.c_void_p()
-        err = errbuf()
-        p0, _k0 = cstr_array(pool0)
-        p1, _k1 = cstr_array(pool1)
-        check(L.scg_plan_combo(C.byref(h), template.encode(), int(strand), p0, len(pool0), p1, len(pool1), int(mismatches),
-                               int(bool(use_first)), int(device), err, _lib.ERRCAP), err)
-        return cls(h.value, "combo", (len(pool0), len(pool1)), device)
+        return cls._new("scg_plan_combo", (template.encode(), int(strand), *_lib.pool(pool0), *_lib.pool(pool1), int(mismatches),
+                                           int(bool(use_first))), "combo", (len(pool0), len(pool1)), device)
 
     @classmethod
     def dual(cls, template1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],
@@ -117,27 +131,17 @@ class Plan:
         if len(pool1) != len(pool2):
             # kaori/handlers/DualBarcodesPairedEnd.hpp:106-109
             raise ScgError(_lib.SCG_ERR_INVALID, "both barcode pools should be of the same length")
-        L = _lib.load()
-        h = C.c_void_p()
-        err = errbuf()
-        p1, _k1 = cstr_array(pool1)
-        p2, _k2 = cstr_array(pool2)
-        check(L.scg_plan_dual(C.byref(h), template1.encode(), int(bool(reverse1)), int(mismatches1), p1,
-                              template2.encode(), int(bool(reverse2)), int(mismatches2), p2, len(pool1),
-                              int(bool(randomized)), int(bool(use_first)), int(bool(diagnostics)), int(device), err, _lib.ERRCAP), err)
-        return cls(h.value, "dual", (len(pool1),), device)
+        return cls._new("scg_plan_dual", (template1.encode(), int(bool(reverse1)), int(mismatches1), cstr_array(pool1)[0],
+                                          template2.encode(), int(bool(reverse2)), int(mismatches2), cstr_array(pool2)[0], len(pool1),
+                                          int(bool(randomized)), int(bool(use_first)), int(bool(diagnostics))), "dual", (len(pool1),), device)
 
     @classmethod
     def dual_single_end(cls, template: str, strand: int, pools: Sequence[Sequence[str]], mismatches: int = 0,
                         use_first: bool = True, device: int = -1) -> "Plan":
         """countDualBarcodesSingleEnd: counted with count(), read with read()."""
-        L = _lib.load()
-        h = C.c_void_p()
-        err = errbuf()
         rows, sizes, _keep = _lib.cstr_matrix(pools)
-        check(L.scg_plan_dual_single_end(C.byref(h), template.encode(), int(strand), rows, sizes, len(pools),
-                                         int(mismatches), int(bool(use_first)), int(device), err, _lib.ERRCAP), err)
-        return cls(h.value, "single", (len(pools[0]) if pools else 0,), device)
+        return cls._new("scg_plan_dual_single_end", (template.encode(), int(strand), rows, sizes, len(pools), int(mismatches),
+                                                     int(bool(use_first))), "single", (len(pools[0]) if pools else 0,), device)
 
     @classmethod
     def paired_combo(cls, template1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],
@@ -145,25 +149,14 @@ class Plan:
                      randomized: bool = False, use_first: bool = True, device: int = -1) -> "Plan":
         """countPairedComboBarcodes: counted with count_paired(), read with read_diagnostics()
         (indices/freq = the combinations; `counts` is empty)."""
-        L = _lib.load()
-        h = C.c_void_p()
-        err = errbuf()
-        p1, _k1 = cstr_array(pool1)
-        p2, _k2 = cstr_array(pool2)
-        check(L.scg_plan_paired_combo(C.byref(h), template1.encode(), int(bool(reverse1)), int(mismatches1), p1, len(pool1),
-                                      template2.encode(), int(bool(reverse2)), int(mismatches2), p2, len(pool2),
-                                      int(bool(randomized)), int(bool(use_first)), int(device), err, _lib.ERRCAP), err)
-        return cls(h.value, "dual", (0,), device)
+        return cls._new("scg_plan_paired_combo", (template1.encode(), int(bool(reverse1)), int(mismatches1), *_lib.pool(pool1),
+                                                  template2.encode(), int(bool(reverse2)), int(mismatches2), *_lib.pool(pool2),
+                                                  int(bool(randomized)), int(bool(use_first))), "dual", (0,), device)
 
     @classmethod
     def random(cls, template: str, strand: int, mismatches: int = 0, use_first: bool = True, device: int = -1) -> "Plan":
         """countRandomBarcodes: counted with count(), read with read_random().  The tally stays in HBM between batches."""
-        L = _lib.load()
-        h = C.c_void_p()
-        err = errbuf()
-        check(L.scg_plan_random(C.byref(h), template.encode(), int(strand), int(mismatches), int(bool(use_first)), int(device),
-                                err, _lib.ERRCAP), err)
-        return cls(h.value, "random", (0,), device)
+        return cls._new("scg_plan_random", (template.encode(), int(strand), int(mismatches), int(bool(use_first))), "random", (0,), device)
 
     def close(self) -> None:
         if self._h:
@@ -207,16 +200,8 @@ class Plan:
         max_len (ragged batches): upper bound on the read lengths if known; a tile-shape hint only."""
         _check_u8(seqs, "seqs")
         _check_offsets(offsets, "offsets")
-        if offsets is not None:
-            n = offsets.numel() - 1 if n_reads is None else n_reads
-            if max_len <= 0 and n > 0:
-                max_len = _max_len(offsets, n)
-        else:
-            if fixed_len <= 0:
-                raise ValueError("either offsets or a positive fixed_len is required")
-            n = seqs.numel() // fixed_len if n_reads is None else n_reads
-            if n * fixed_len > seqs.numel():
-                raise ValueError("seqs is shorter than n_reads * fixed_len")
+        n = _batch_reads(seqs, offsets, fixed_len, n_reads)
+        max_len = _batch_max_len(offsets, fixed_len, n, max_len)
         err = errbuf()
         check(self._lib.scg_count_batch(self._h, C.c_void_p(_dev_ptr(seqs)), C.c_void_p(_dev_ptr(offsets)), int(fixed_len),
                                         int(max_len), int(n), C.c_void_p(_stream_handle(stream)), err, _lib.ERRCAP), err)
@@ -233,16 +218,8 @@ class Plan:
         unknown = [f for f in fields if f not in ASSIGN_FIELDS]
         if unknown or "index" not in fields:
             raise ValueError(f"fields must name 'index' and any of {ASSIGN_FIELDS[1:]} (got {tuple(fields)})")
-        if offsets is not None:
-            n = offsets.numel() - 1 if n_reads is None else n_reads
-            if max_len <= 0 and n > 0:
-                max_len = _max_len(offsets, n)
-        else:
-            if fixed_len <= 0:
-                raise ValueError("either offsets or a positive fixed_len is required")
-            n = seqs.numel() // fixed_len if n_reads is None else n_reads
-            if n * fixed_len > seqs.numel():
-                raise ValueError("seqs is shorter than n_reads * fixed_len")
+        n = _batch_reads(seqs, offsets, fixed_len, n_reads)
+        max_len = _batch_max_len(offsets, fixed_len, n, max_len)
         with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
             # (allocated on the launch stream, so that the caching allocator orders their reuse with the kernel)
             out = [torch.empty(int(n), dtype=torch.int32 if f in ("index", "position") else torch.int8, device=seqs.device)
@@ -259,14 +236,7 @@ class Plan:
         _check_u8(seqs2, "seqs2")
         _check_offsets(offsets1, "offsets1")
         _check_offsets(offsets2, "offsets2")
-
-        def count_of(seqs, offs, fl):
-            if offs is not None:
-                return offs.numel() - 1
-            if fl <= 0:
-                raise ValueError("either offsets or a positive fixed_len is required")
-            return seqs.numel() // fl
-        n1, n2 = count_of(seqs1, offsets1, fixed_len1), count_of(seqs2, offsets2, fixed_len2)
+        n1, n2 = _batch_reads(seqs1, offsets1, fixed_len1), _batch_reads(seqs2, offsets2, fixed_len2)
         if n_pairs is None:
             if n1 != n2:
                 # kaori/process_data.hpp:284-285
@@ -274,10 +244,7 @@ class Plan:
             n_pairs = n1
         elif n_pairs > min(n1, n2):
             raise ValueError("n_pairs exceeds the batch")
-        if max_len <= 0 and n_pairs > 0:
-            m1 = fixed_len1 if offsets1 is None else _max_len(offsets1, n_pairs)
-            m2 = fixed_len2 if offsets2 is None else _max_len(offsets2, n_pairs)
-            max_len = max(m1, m2)
+        max_len = max(_batch_max_len(offsets1, fixed_len1, n_pairs, max_len), _batch_max_len(offsets2, fixed_len2, n_pairs, max_len))
         err = errbuf()
         check(self._lib.scg_count_batch_paired(self._h, C.c_void_p(_dev_ptr(seqs1)), C.c_void_p(_dev_ptr(offsets1)), int(fixed_len1),
                                                C.c_void_p(_dev_ptr(seqs2)), C.c_void_p(_dev_ptr(offsets2)), int(fixed_len2),
@@ -296,21 +263,13 @@ class Plan:
         """Dual plans built with diagnostics=True -> dict(counts, indices int32[2, K], freq, total,
         barcode1_only, barcode2_only), the outputs of src/count_dual_barcodes.cpp:64-70."""
         counts = np.zeros(max(self.n_pool[0], 1), dtype=np.int32)
-        idx_p, freq_p = _lib.i32_p(), _lib.i32_p()
-        k, total = C.c_int64(0), C.c_int64(0)
-        b1, b2 = C.c_int32(0), C.c_int32(0)
+        total, b1, b2 = C.c_int64(0), C.c_int32(0), C.c_int32(0)
         err = errbuf()
-        check(self._lib.scg_plan_read_diagnostics(self._h, counts.ctypes.data_as(_lib.i32_p), C.byref(idx_p), C.byref(freq_p),
-                                                  C.byref(k), C.byref(total), C.byref(b1), C.byref(b2),
-                                                  C.c_void_p(_stream_handle(stream)), err, _lib.ERRCAP), err)
-        K = int(k.value)
-        try:
-            idx = np.ctypeslib.as_array(idx_p, shape=(max(2 * K, 1),))[:2 * K].reshape(K, 2).T.copy()
-            freq = np.ctypeslib.as_array(freq_p, shape=(max(K, 1),))[:K].copy()
-        finally:
-            self._lib.scg_free(idx_p)
-            self._lib.scg_free(freq_p)
-        return dict(counts=counts[:self.n_pool[0]].copy(), indices=idx.astype(np.int32), freq=freq.astype(np.int32),
+        with combo_outputs(self._lib) as (combos, take):
+            check(self._lib.scg_plan_read_diagnostics(self._h, counts.ctypes.data_as(_lib.i32_p), *combos, C.byref(total), C.byref(b1),
+                                                      C.byref(b2), C.c_void_p(_stream_handle(stream)), err, _lib.ERRCAP), err)
+            idx, freq = take()
+        return dict(counts=counts[:self.n_pool[0]].copy(), indices=idx, freq=freq,
                     total=int(total.value), barcode1_only=int(b1.value), barcode2_only=int(b2.value))
 
     def read_combo(self, stream=None):
@@ -318,19 +277,13 @@ class Plan:
         for combination spaces beyond 2^26 cells, from the sorted, run-length encoded combination streams."""
         if self.kind != "combo":
             raise ValueError("read_combo needs a combo plan")
-        idx_p, freq_p = _lib.i32_p(), _lib.i32_p()
-        k, total = C.c_int64(0), C.c_int64(0)
+        total = C.c_int64(0)
         err = errbuf()
-        check(self._lib.scg_plan_read_combinations(self._h, C.byref(idx_p), C.byref(freq_p), C.byref(k), C.byref(total),
-                                                   C.c_void_p(_stream_handle(stream)), err, _lib.ERRCAP), err)
-        K = int(k.value)
-        try:
-            idx = np.ctypeslib.as_array(idx_p, shape=(max(2 * K, 1),))[:2 * K].reshape(K, 2).T.copy()
-            freq = np.ctypeslib.as_array(freq_p, shape=(max(K, 1),))[:K].copy()
-        finally:
-            self._lib.scg_free(idx_p)
-            self._lib.scg_free(freq_p)
-        return idx.astype(np.int32), freq.astype(np.int32), int(total.value)
+        with combo_outputs(self._lib) as (combos, take):
+            check(self._lib.scg_plan_read_combinations(self._h, *combos, C.byref(total), C.c_void_p(_stream_handle(stream)),
+                                                       err, _lib.ERRCAP), err)
+            idx, freq = take()
+        return idx, freq, int(total.value)
 
     def read_random(self, stream=None):
         """Random-barcode plans: ((keys list[str] sorted byte-wise, freq int32[K]), total reads) of every batch counted
@@ -343,10 +296,9 @@ class Plan:
                                             C.c_void_p(_stream_handle(stream)), err, _lib.ERRCAP)
         try:
             check(rc, err)
-            K, W = int(k.value), int(vlen.value)
-            blob = C.string_at(seq_p, K * (W + 1)) if K else b""
-            seqs = [blob[i * (W + 1): i * (W + 1) + W].decode("latin-1") for i in range(K)]
-            freq = np.ctypeslib.as_array(freq_p, shape=(max(K, 1),))[:K].copy().astype(np.int32) if K else np.zeros(0, dtype=np.int32)
+            K = int(k.value)
+            seqs = _lib.decode_sequences(seq_p, K, int(vlen.value))
+            freq = np.ctypeslib.as_array(freq_p, shape=(K,)).copy() if K else np.zeros(0, dtype=np.int32)
         finally:
             self._lib.scg_free(seq_p)
             self._lib.scg_free(freq_p)
@@ -372,21 +324,11 @@ def combo_compact(cells: np.ndarray, n0: int, n1: int):
     cells = np.ascontiguousarray(cells, dtype=np.int32)
     if cells.size < n0 * n1:
         raise ValueError("cells too short")
-    idx_p = _lib.i32_p()
-    freq_p = _lib.i32_p()
-    k = C.c_int64(0)
     err = errbuf()
     src = cells if cells.size else np.zeros(1, dtype=np.int32)
-    check(L.scg_combo_compact(src.ctypes.data_as(_lib.i32_p), int(n0), int(n1), C.byref(idx_p), C.byref(freq_p), C.byref(k),
-                              err, _lib.ERRCAP), err)
-    K = int(k.value)
-    try:
-        idx = np.ctypeslib.as_array(idx_p, shape=(max(2 * K, 1),))[:2 * K].reshape(K, 2).T.copy()
-        freq = np.ctypeslib.as_array(freq_p, shape=(max(K, 1),))[:K].copy()
-    finally:
-        L.scg_free(idx_p)
-        L.scg_free(freq_p)
-    return idx.astype(np.int32), freq.astype(np.int32)
+    with combo_outputs(L) as (combos, take):
+        check(L.scg_combo_compact(src.ctypes.data_as(_lib.i32_p), int(n0), int(n1), *combos, err, _lib.ERRCAP), err)
+        return take()
 
 
 def upload_reads(reads, device="cuda"):

@@ -23,6 +23,44 @@ std::vector<const char*> borrow(const Rcpp::CharacterVector& x) {
     return p;
 }
 void check(int rc, const char* err) { if (rc != SCG_OK) Rcpp::stop(err); }
+
+// Combinations as libscg hands them out (malloc'd: 2 x K indices, column-major and 0-based, sorted by (first, second); K
+// frequencies) -> what R gets.
+Rcpp::IntegerMatrix combination_indices(const int32_t* idx, int64_t k) {
+    Rcpp::IntegerMatrix m(2, k);
+    std::copy(idx, idx + 2 * k, m.begin());
+    return m;
+}
+Rcpp::IntegerVector combination_counts(const int32_t* freq, int64_t k) { return Rcpp::IntegerVector(freq, freq + k); }
+
+// The (indices, frequencies, K) outputs of a one-file entry.  Released when this goes out of scope: after the copies are
+// made, and also when an allocation on the R side throws before that.
+struct Combinations {
+    int32_t *idx = nullptr, *freq = nullptr;
+    int64_t k = 0;
+    Combinations() {}
+    Combinations(const Combinations&) = delete;
+    Combinations& operator=(const Combinations&) = delete;
+    ~Combinations() { scg_free(idx); scg_free(freq); }
+    Rcpp::IntegerMatrix indices() const { return combination_indices(idx, k); }
+    Rcpp::IntegerVector counts() const { return combination_counts(freq, k); }
+    Rcpp::List both() const { return Rcpp::List::create(indices(), counts()); }
+};
+
+// The same per file, in the arrays of n_files entries a many-files entry fills: file f's 2 x K_f matrix of indices and its
+// K_f frequencies.  All of them are released when this goes out of scope, also when an allocation on the R side throws
+// half-way through the files.
+struct PerFileCombinations {
+    std::vector<int32_t*> idx, freq;
+    std::vector<int64_t> k;
+    explicit PerFileCombinations(size_t n_files) : idx(n_files, nullptr), freq(n_files, nullptr), k(n_files, 0) {}
+    PerFileCombinations(const PerFileCombinations&) = delete;
+    PerFileCombinations& operator=(const PerFileCombinations&) = delete;
+    ~PerFileCombinations() { for (size_t f = 0; f < idx.size(); ++f) { scg_free(idx[f]); scg_free(freq[f]); } }
+    Rcpp::IntegerMatrix indices(R_xlen_t f) const { return combination_indices(idx[f], k[f]); }
+    Rcpp::IntegerVector counts(R_xlen_t f) const { return combination_counts(freq[f], k[f]); }
+    Rcpp::List both(R_xlen_t f) const { return Rcpp::List::create(indices(f), counts(f)); }
+};
 }
 
 //[[Rcpp::export(rng=false)]]
@@ -43,16 +81,12 @@ Rcpp::List count_combo_barcodes_single(std::string path, std::string constant, i
     if (pool.size() != 2) Rcpp::stop("currently expecting only 2 variable regions for single-end combinatorial barcodes");
     Rcpp::CharacterVector c0(pool[0]), c1(pool[1]);
     auto p0 = borrow(c0), p1 = borrow(c1);
-    int32_t *idx = nullptr, *freq = nullptr; int64_t k = 0; int total = 0;
+    Combinations found; int total = 0;
     char err[1024];
     check(scg_count_combo_barcodes_single(path.c_str(), constant.c_str(), strand, p0.data(), (int32_t)p0.size(),
                                           p1.data(), (int32_t)p1.size(), mismatches, use_first, nthreads,
-                                          &idx, &freq, &k, &total, err, sizeof(err)), err);
-    Rcpp::IntegerMatrix indices(2, k);                  // column-major 2 x K, 0-based, sorted by (first, second)
-    std::copy(idx, idx + 2 * k, indices.begin());
-    Rcpp::IntegerVector counts(freq, freq + k);
-    scg_free(idx); scg_free(freq);
-    return Rcpp::List::create(indices, counts, Rcpp::IntegerVector::create(total));   // src/count_combo_barcodes_single.cpp:32-36
+                                          &found.idx, &found.freq, &found.k, &total, err, sizeof(err)), err);
+    return Rcpp::List::create(found.indices(), found.counts(), Rcpp::IntegerVector::create(total));   // src/count_combo_barcodes_single.cpp:32-36
 }
 
 //[[Rcpp::export(rng=false)]]
@@ -65,16 +99,12 @@ Rcpp::List count_dual_barcodes(std::string path1, std::string constant1, bool re
     int total = 0;
     char err[1024];
     if (diagnostics) {                                  // include.invalid=TRUE: 5-list of src/count_dual_barcodes.cpp:64-70
-        int32_t *idx = nullptr, *freq = nullptr; int64_t k = 0; int b1 = 0, b2 = 0;
+        Combinations invalid; int b1 = 0, b2 = 0;
         check(scg_count_dual_barcodes_diagnostics(path1.c_str(), constant1.c_str(), reverse1, mismatches1, p1.data(),
                                                   path2.c_str(), constant2.c_str(), reverse2, mismatches2, p2.data(), (int32_t)p1.size(),
-                                                  randomized, use_first, nthreads, counts.begin(), &idx, &freq, &k, &total, &b1, &b2,
-                                                  err, sizeof(err)), err);
-        Rcpp::IntegerMatrix indices(2, k);
-        std::copy(idx, idx + 2 * k, indices.begin());
-        Rcpp::IntegerVector invalid(freq, freq + k);
-        scg_free(idx); scg_free(freq);
-        return Rcpp::List::create(counts, Rcpp::List::create(indices, invalid), Rcpp::IntegerVector::create(total),
+                                                  randomized, use_first, nthreads, counts.begin(), &invalid.idx, &invalid.freq, &invalid.k,
+                                                  &total, &b1, &b2, err, sizeof(err)), err);
+        return Rcpp::List::create(counts, invalid.both(), Rcpp::IntegerVector::create(total),
                                   Rcpp::IntegerVector::create(b1), Rcpp::IntegerVector::create(b2));
     }
     check(scg_count_dual_barcodes(path1.c_str(), constant1.c_str(), reverse1, mismatches1, p1.data(),
@@ -111,15 +141,11 @@ Rcpp::List count_dual_barcodes_single_end(std::string path, std::string constant
     int total = 0;
     char err[1024];
     if (diagnostics) {                                  // 3-list of src/count_dual_barcodes_single_end.cpp:44-48
-        int32_t *idx = nullptr, *freq = nullptr; int64_t k = 0;
+        Combinations invalid;
         check(scg_count_dual_barcodes_single_end_diagnostics(path.c_str(), constant.c_str(), rows.data(), sizes.data(), (int32_t)rows.size(),
-                                                             strand, mismatches, use_first, nthreads, counts.begin(), &idx, &freq, &k, &total,
-                                                             err, sizeof(err)), err);
-        Rcpp::IntegerMatrix indices(2, k);
-        std::copy(idx, idx + 2 * k, indices.begin());
-        Rcpp::IntegerVector invalid(freq, freq + k);
-        scg_free(idx); scg_free(freq);
-        return Rcpp::List::create(counts, Rcpp::List::create(indices, invalid), Rcpp::IntegerVector::create(total));
+                                                             strand, mismatches, use_first, nthreads, counts.begin(),
+                                                             &invalid.idx, &invalid.freq, &invalid.k, &total, err, sizeof(err)), err);
+        return Rcpp::List::create(counts, invalid.both(), Rcpp::IntegerVector::create(total));
     }
     check(scg_count_dual_barcodes_single_end(path.c_str(), constant.c_str(), rows.data(), sizes.data(), (int32_t)rows.size(),
                                              strand, mismatches, use_first, diagnostics, nthreads, counts.begin(), &total, err, sizeof(err)), err);
@@ -131,16 +157,13 @@ Rcpp::List count_combo_barcodes_paired(std::string path1, std::string constant1,
                                        std::string path2, std::string constant2, bool reverse2, int mismatches2, Rcpp::CharacterVector pool2,
                                        bool randomized, bool use_first, int nthreads) {
     auto p1 = borrow(pool1), p2 = borrow(pool2);
-    int32_t *idx = nullptr, *freq = nullptr; int64_t k = 0; int total = 0, b1 = 0, b2 = 0;
+    Combinations found; int total = 0, b1 = 0, b2 = 0;
     char err[1024];
     check(scg_count_combo_barcodes_paired(path1.c_str(), constant1.c_str(), reverse1, mismatches1, p1.data(), (int32_t)p1.size(),
                                           path2.c_str(), constant2.c_str(), reverse2, mismatches2, p2.data(), (int32_t)p2.size(),
-                                          randomized, use_first, nthreads, &idx, &freq, &k, &total, &b1, &b2, err, sizeof(err)), err);
-    Rcpp::IntegerMatrix indices(2, k);
-    std::copy(idx, idx + 2 * k, indices.begin());
-    Rcpp::IntegerVector counts(freq, freq + k);
-    scg_free(idx); scg_free(freq);
-    return Rcpp::List::create(indices, counts, Rcpp::IntegerVector::create(total),          // src/count_combo_barcodes_paired.cpp:47-54
+                                          randomized, use_first, nthreads, &found.idx, &found.freq, &found.k, &total, &b1, &b2,
+                                          err, sizeof(err)), err);
+    return Rcpp::List::create(found.indices(), found.counts(), Rcpp::IntegerVector::create(total),   // src/count_combo_barcodes_paired.cpp:47-54
                               Rcpp::IntegerVector::create(b1), Rcpp::IntegerVector::create(b2));
 }
 
@@ -166,26 +189,6 @@ Rcpp::List match_barcodes(Rcpp::CharacterVector sequences, Rcpp::CharacterVector
 // goes for matrixOfDualBarcodes (with and without include.invalid), matrixOfDualBarcodesSingleEnd (likewise),
 // matrixOfPairedComboBarcodes and matrixOfRandomBarcodes: INTEGRATION.md lists which wrapper reaches which export.
 // ---------------------------------------------------------------------------------------------------------------
-
-namespace {
-// The per-file malloc'd outputs of a many-files entry: file f's 2 x K_f matrix of indices and its K_f frequencies.  All of
-// them are released when this goes out of scope, also when an allocation on the R side throws half-way through the files.
-struct PerFileCombinations {
-    std::vector<int32_t*> idx, freq;
-    std::vector<int64_t> k;
-    explicit PerFileCombinations(size_t n_files) : idx(n_files, nullptr), freq(n_files, nullptr), k(n_files, 0) {}
-    PerFileCombinations(const PerFileCombinations&) = delete;
-    PerFileCombinations& operator=(const PerFileCombinations&) = delete;
-    ~PerFileCombinations() { for (size_t f = 0; f < idx.size(); ++f) { scg_free(idx[f]); scg_free(freq[f]); } }
-    Rcpp::IntegerMatrix indices(R_xlen_t f) const {
-        Rcpp::IntegerMatrix m(2, k[f]);
-        std::copy(idx[f], idx[f] + 2 * k[f], m.begin());
-        return m;
-    }
-    Rcpp::IntegerVector counts(R_xlen_t f) const { return Rcpp::IntegerVector(freq[f], freq[f] + k[f]); }
-    Rcpp::List both(R_xlen_t f) const { return Rcpp::List::create(indices(f), counts(f)); }
-};
-}
 
 //[[Rcpp::export(rng=false)]]
 Rcpp::List count_single_barcodes_files(Rcpp::CharacterVector paths, std::string constant, int strand, Rcpp::CharacterVector pool,
