@@ -36,18 +36,10 @@
 namespace scg {
 namespace {
 
-// CRC-32 of a text from the CRCs of its pieces: crc(A B) = crc(A) * x^(8 |B|) + crc(B) over GF(2) modulo the CRC polynomial
-// (reflected: bit 31 is x^0) -- zlib's crc32_combine, whose 1.2.11 form squares a 32 x 32 matrix per call; thousands of
-// pieces of one length need the power only once.
-uint32_t gf2_mult(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (int i = 0; i < 32 && a; ++i) {
-        if (a & 0x80000000u) p ^= b;
-        a <<= 1;
-        b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-    }
-    return p;
-}
+// x^(8 len) modulo the CRC polynomial, for scginf::gf2_mult's combining of piece CRCs (scg_inflate.h): zlib's
+// crc32_combine in its 1.2.11 form squares a 32 x 32 matrix per call; thousands of pieces of one length need the power
+// only once.
+using scginf::gf2_mult;
 uint32_t x_pow_bytes(uint64_t len) {                   // x^(8 len)
     uint32_t sq = 0x40000000u, x = 0x80000000u;         // x^1, x^0
     for (int k = 0; k < 3; ++k) sq = gf2_mult(sq, sq);

@@ -1,19 +1,30 @@
-// scg_inflate.h -- DEFLATE (RFC 1951) decoder for one gzip member, written to run one member per GPU wavefront.
+// scg_inflate.h -- the DEFLATE (RFC 1951) rules of the device decoders, and the decoder that walks one gzip member
+// with a whole wavefront.
 //
 // BGZF files ("blocked gzip", what bgzip writes) are a concatenation of small independent gzip members (<= 64 KiB of
 // text each) that announce their compressed size; the reference inflates them one after the other on the caller
 // thread (byteme/GzipFileReader.hpp:39-51 -> zlib).  Here the compressed bytes cross the PCIe link as they are and
-// every wavefront of scg_inflate.hip's kernel inflates one member, its Huffman tables in LDS; the text never exists
-// on the host.  Decoding is a chain of dependent steps, so all lanes of the wavefront walk it together (every value
-// below is wave-uniform: the compiler keeps the decoder's state in scalar registers) and the lanes only differ where
-// bytes move: a match is copied 64 bytes at a time, one per lane.  The function is plain C++ so that the very same code
-// can be compiled for the host by the tests (tests/inflate_harness.cpp: differential runs against zlib, corrupted
-// streams under ASan) with a "wavefront" of one lane; the product only ever runs it on the device.
+// every wavefront of scg_inflate.hip's kernels inflates one member (or one chunk of an ordinary gzip stream), its
+// Huffman tables in LDS; the text never exists on the host.
+//
+// Two decoders share what is a rule of the format -- the bit reader, block headers and their tables (fixed_tables,
+// read_dynamic_tables), the length and distance symbols (length_* / dist_*, read_match, decode_here), a match's copy
+// (copy_match):
+//   * the lane-parallel decoder (scg_inflate.hip: inflate_lanes; the product's default, and stage 1 of the gzip path)
+//     decodes 128 bit offsets at a time with decode_here and keeps only its scheduling -- batches, the chain walk,
+//     deferred matches -- in the device file;
+//   * inflate_member below (SCG_INFLATE_LANES=0: a measurement and test aid) walks the chain of dependent steps with
+//     all lanes together: every value is wave-uniform, the compiler keeps the decoder's state in scalar registers, and
+//     the lanes only differ where bytes move (a match is copied 64 bytes at a time, one per lane).
+// Everything is plain C++, so the tests compile the very same code for the host (tests/inflate_harness.cpp:
+// differential runs against zlib, corrupted streams under ASan): inflate_member with "wavefronts" of 1, 7 and 64
+// lanes, and a model of the lane-parallel decoder's arithmetic built from the same functions.  The CRC code's GF(2)
+// multiply (gf2_mult, at the end) lives here too, for the device's CRC kernel and the host side of the gzip path.
 //
 // Accept / reject behaviour follows zlib's inflate (inflate.c, inftrees.c) rule by rule -- over-subscribed and
 // incomplete code sets, missing end-of-block code, too many length / distance symbols, invalid stored block lengths,
-// distances beyond the start of the member -- because a member this decoder accepts is not looked at by zlib again.
-// Whatever it rejects is redone by the host path, whose errors are zlib's own.  Every loop is bounded by the member's
+// distances beyond the start of the member -- because a member these decoders accept is not looked at by zlib again.
+// Whatever they reject is redone by the host path, whose errors are zlib's own.  Every loop is bounded by the member's
 // compressed and inflated sizes: a corrupt stream ends in an error, never in a runaway lane.
 #ifndef SCG_INFLATE_H
 #define SCG_INFLATE_H
@@ -34,21 +45,26 @@ enum : int {
     INFLATE_BAD_SIZE = 2,      // valid so far, but it does not fill / overruns the announced sizes
 };
 
-constexpr int LIT_BITS = 9;       // primary table of the literal/length code
-constexpr int DIST_BITS = 7;      // primary table of the distance code
+constexpr int LIT_BITS = 9, DIST_BITS = 7;                   // primary tables of the literal/length and the distance code: inflate_member
+constexpr int LANES_LIT_BITS = 10, LANES_DIST_BITS = 8;      // the lane-parallel decoder (11 / 9 bits: no gain -- long codes are rare in FASTQ)
+constexpr int CL_BITS = 7;                                   // the code-length code's longest code
 constexpr uint32_t IN_SLACK = 64; // bytes readable beyond a member's payload (the caller pads its buffer)
 
-// One member's tables (LDS on the device, one set per wavefront): 2016 bytes.
-struct LaneTables {
-    uint16_t lit[1 << LIT_BITS];      // (code length << 12) | symbol, 0 = the code is longer than LIT_BITS (or invalid);
-                                      // while a dynamic header is read, the code lengths live here (bytes)
-    uint16_t dtab[1 << DIST_BITS];    // the same for distance codes; during the header: the code-length code's table
+// One block's tables (LDS on the device, one set per wavefront).
+template<int LIT, int DIST>
+struct Tables {
+    static constexpr int lit_bits = LIT, dist_bits = DIST;
+    uint16_t lit[1 << LIT];           // (code length << 12) | symbol, 0 = the code is longer than LIT bits (or invalid);
+                                      // while a block header is read, the code lengths live here (bytes: 320 + 19 of them)
+    uint16_t dtab[1 << DIST];         // the same for distance codes; during the header: the code-length code's table
     uint16_t lsym[288];               // literal/length symbols sorted by (code length, symbol)
     uint16_t dsym[32];
     uint16_t lcount[16];              // number of codes of each length
     uint16_t dcount[16];
     uint16_t offs[16];                // scratch of the table builder
 };
+typedef Tables<LIT_BITS, DIST_BITS> LaneTables;                   // 2016 bytes
+typedef Tables<LANES_LIT_BITS, LANES_DIST_BITS> WaveTables;       // 3.3 KB
 
 // The lanes that walk a member together ("Wave" below).  The decoder's own state is the same in every lane; the lanes
 // differ only inside a Wave::Vec, a vector with one byte per lane, which the decoder moves around but never looks into:
@@ -94,6 +110,14 @@ struct BitReader {
         a0 = load32(in);
         a1 = load32(in + 4);
     }
+    // Stands at bit `bit` of the stream afterwards, with at least 33 bits in the buffer.
+    SCG_HD void open_at_bit(const uint8_t* p, uint32_t n, uint32_t bit) {
+        open(p, n);
+        seek(bit >> 3);
+        refill();
+        bits(bit & 7u);
+        refill();
+    }
     // Continues at byte `at` of the stream (bit buffer empty).
     SCG_HD void seek(uint32_t at) {
         pos = at; buf = 0; cnt = 0;
@@ -116,6 +140,7 @@ struct BitReader {
         cnt -= n;
         return v;
     }
+    SCG_HD uint32_t bit_position() const { return pos * 8u - cnt; }     // of the next unread bit
     SCG_HD bool overrun() const { return pos > len + 8; }     // more than the refill look-ahead beyond the payload
 };
 
@@ -260,6 +285,183 @@ SCG_HD int decode_symbol(BitReader& br, const uint16_t* table, int tbits, const 
     return decode_slow(br, count, sym);
 }
 
+// Length symbol 257 + t, t <= 28: its extra bits and its base; distance symbol d <= 29 likewise.
+SCG_HD uint32_t length_extra(uint32_t t) { return (t < 8u || t == 28u) ? 0u : (t - 4u) >> 2; }
+SCG_HD uint32_t length_base(uint32_t t, uint32_t eb) { return t < 8u ? t + 3u : (t == 28u ? 258u : ((4u + (t & 3u)) << eb) + 3u); }
+SCG_HD uint32_t dist_extra(uint32_t d) { return d < 4u ? 0u : (d >> 1) - 1u; }
+SCG_HD uint32_t dist_base(uint32_t d, uint32_t eb) { return d < 4u ? d + 1u : ((2u + (d & 1u)) << eb) + 1u; }
+
+// The match that begins with literal/length symbol s > 256, which has just been read: the length's extra bits, the
+// distance code and its extra bits.  False for a symbol or a distance code that is none.  Needs 33 bits in the reader.
+template<class TablesT>
+SCG_HD bool read_match(BitReader& br, const TablesT& T, int s, uint32_t& n, uint32_t& dist) {
+    if (s > 285) return false;                                           // "invalid literal/length code"
+    const uint32_t lt = static_cast<uint32_t>(s) - 257u, leb = length_extra(lt);
+    n = length_base(lt, leb) + br.bits(leb);
+    br.refill();
+    const int d = decode_symbol(br, T.dtab, TablesT::dist_bits, T.dcount, T.dsym);
+    if (d < 0 || d >= 30) return false;                                  // "invalid distance code"
+    const uint32_t deb = dist_extra(static_cast<uint32_t>(d));
+    dist = dist_base(static_cast<uint32_t>(d), deb) + br.bits(deb);
+    return true;
+}
+
+// What the code starting at the low end of `w` would be (>= 57 valid bits), were it a code start.
+// kind: 0 literal, 1 match, 2 end of block, 3 "not decodable here" (long code / invalid: the chain stops)
+struct LaneCode {
+    uint32_t kind, adv, outlen, n, dist, sym;
+};
+template<class TablesT>
+SCG_HD LaneCode decode_here(const TablesT& T, uint64_t w) {
+    // Straight-line: every lane goes through the length and the distance arithmetic, whatever its code is, and the
+    // results are selected at the end.  As nested branches this cost 13 exec-mask save / restore pairs and 40 register
+    // moves per 64 offsets -- scalar instructions the whole wavefront waits for, most of them for offsets that are no code
+    // starts anyway.
+    LaneCode c;
+    const uint32_t e = T.lit[static_cast<uint32_t>(w) & ((1u << TablesT::lit_bits) - 1u)];
+    const uint32_t l = e >> 12;
+    c.sym = e & 0xFFFu;
+    const uint32_t t0 = c.sym - 257u;                                   // (wraps for literals: clamped, and not used then)
+    const uint32_t t = t0 < 28u ? t0 : 28u;
+    const uint32_t eb = length_extra(t);
+    const uint32_t base = length_base(t, eb);
+    uint64_t w2 = w >> l;
+    c.n = base + (static_cast<uint32_t>(w2) & ((1u << eb) - 1u));
+    w2 >>= eb;
+    const uint32_t de = T.dtab[static_cast<uint32_t>(w2) & ((1u << TablesT::dist_bits) - 1u)];
+    const uint32_t dl = de >> 12, ds0 = de & 0xFFFu;
+    const uint32_t ds = ds0 < 29u ? ds0 : 29u;
+    const uint32_t deb = dist_extra(ds);
+    const uint32_t dbase = dist_base(ds, deb);
+    w2 >>= dl;
+    c.dist = dbase + (static_cast<uint32_t>(w2) & ((1u << deb) - 1u));
+    const bool is_length = c.sym > 256u && c.sym <= 285u;
+    const bool is_match = is_length && de != 0u && ds0 < 30u;
+    c.kind = e == 0u ? 3u : (c.sym < 256u ? 0u : (c.sym == 256u ? 2u : (is_match ? 1u : 3u)));
+    c.adv = c.kind == 1u ? l + eb + dl + deb : l;
+    c.outlen = c.kind == 0u ? 1u : (c.kind == 1u ? c.n : 0u);
+    return c;
+}
+
+// The two tables of a block from its code lengths, lens[0 .. nlen) and lens[nlen .. nlen + ndist).  The distance code
+// first: its lengths lie in the area the literal/length table is about to take; that table then overwrites its own
+// lengths: the builder reads them before it writes.
+template<class TablesT>
+SCG_HD bool build_tables(TablesT& T, const uint8_t* lens, int nlen, int ndist) {
+    if (!build_code(lens + nlen, ndist, 1, T.dtab, TablesT::dist_bits, T.dcount, T.dsym, T.offs)) return false;     // "invalid distances set"
+    if (!build_code(lens, nlen, 1, T.lit, TablesT::lit_bits, T.lcount, T.lsym, T.offs)) return false;               // "invalid literal/lengths set"
+    return true;
+}
+
+// The tables of the fixed code (inflate.c: fixedtables).
+template<class TablesT>
+SCG_HD bool fixed_tables(TablesT& T, uint8_t* lens) {
+    for (int s = 0; s < 144; ++s) lens[s] = 8;
+    for (int s = 144; s < 256; ++s) lens[s] = 9;
+    for (int s = 256; s < 280; ++s) lens[s] = 7;
+    for (int s = 280; s < 288; ++s) lens[s] = 8;
+    for (int s = 0; s < 32; ++s) lens[288 + s] = 5;
+    return build_tables(T, lens, 288, 32);
+}
+
+// The code lengths of a dynamic-Huffman block header (br stands behind BFINAL and BTYPE) and the block's two tables.
+// False for anything zlib would reject (too many codes, an over-subscribed or incomplete set, no end-of-block code).
+template<class TablesT>
+SCG_HD bool read_dynamic_tables(BitReader& br, TablesT& T, uint8_t* lens) {
+        const int nlen = static_cast<int>(br.bits(5)) + 257;
+    const int ndist = static_cast<int>(br.bits(5)) + 1;
+    const int ncode = static_cast<int>(br.bits(4)) + 4;
+    if (nlen > 286 || ndist > 30) return false;                          // "too many length or distance symbols"
+    // the code-length code: its 19 lengths sit behind the 320 bytes reserved for the lengths proper
+    uint8_t* const cl = lens + 320;
+    // the order of the code-length code's lengths (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15), five bits each
+    const uint64_t order_lo = 0x22caa324e804a30ull, order_hi = 0x3c2e1346cull;
+    for (int i = 0; i < 19; ++i) cl[i] = 0;
+    for (int i = 0; i < ncode; ++i) {
+        br.refill();
+        const uint32_t at = static_cast<uint32_t>((i < 12 ? order_lo >> (5 * i) : order_hi >> (5 * (i - 12))) & 31u);
+        cl[at] = static_cast<uint8_t>(br.bits(3));
+    }
+    // (its symbols and counts borrow the distance code's arrays, which are built afterwards)
+    if (!build_code(cl, 19, 0, T.dtab, CL_BITS, T.dcount, T.dsym, T.offs)) return false;     // "invalid code lengths set"
+    int have = 0;
+    while (have < nlen + ndist) {
+        if (br.overrun()) return false;
+        br.refill();
+        const int s = decode_symbol(br, T.dtab, CL_BITS, T.dcount, T.dsym);
+        if (s < 0) return false;
+        if (s < 16) { lens[have++] = static_cast<uint8_t>(s); continue; }
+        uint8_t fill = 0;
+        int rep;
+        if (s == 16) {
+            if (have == 0) return false;                                 // "invalid bit length repeat"
+            fill = lens[have - 1];
+            rep = 3 + static_cast<int>(br.bits(2));
+        } else if (s == 17) {
+            rep = 3 + static_cast<int>(br.bits(3));
+        } else {
+            rep = 11 + static_cast<int>(br.bits(7));
+        }
+        if (have + rep > nlen + ndist) return false;                     // "invalid bit length repeat"
+        while (rep--) lens[have++] = fill;
+    }
+    if (lens[256] == 0) return false;                                    // "invalid code -- missing end-of-block"
+    return build_tables(T, lens, nlen, ndist);
+}
+
+// The decoder writes bytes (BGZF members: the text itself) or 16-bit symbols (chunks of an ordinary gzip stream, decoded
+// without the 32 KiB of text in front of them: a symbol is a byte, or MARKER + k for "byte k of the window I do not have";
+// scg_pgzip.h).  In symbol mode a match may reach in front of the chunk's first symbol: those positions read as markers.
+constexpr uint32_t MARKER = 0x8000u, MARKER_WINDOW = 32768u;
+
+// What stands `-from` symbols in front of the chunk (from < 0).
+SCG_HD uint16_t marker_before(int32_t from) { return static_cast<uint16_t>(MARKER + MARKER_WINDOW + from); }
+
+// One match, copied by one lane: out[at + j] = out[at - d + j], j < len, in that order (d < len: a pattern of period d).
+// E is a byte or a 16-bit symbol, W of them to a word.  A source at least a word back is moved in 8-byte words (up to
+// four loads in flight); a closer one is a pattern of period d, built once in a register and stored over and over.
+// Writes nothing beyond at + len.  READS whole words: for d < W the W elements from at - d on, so up to W - 1 elements
+// at and behind `at` that are not text yet (never used), of which W - d - len (4 bytes at the most, no symbols) may lie
+// beyond at + len: the buffer owns that slack.  In bytes d <= at is the caller's business; in symbols a match that
+// begins in front of the chunk goes symbol by symbol.
+template<class E>
+SCG_HD void copy_match(E* out, uint32_t at, uint32_t len, uint32_t d) {
+    constexpr uint32_t W = 8 / sizeof(E), BITS = 8 * sizeof(E);
+    E* dst = out + at;
+    if (sizeof(E) == 2 && at < d) {
+        for (uint32_t j = 0; j < len; ++j) {
+            const int32_t from = static_cast<int32_t>(at + j) - static_cast<int32_t>(d);
+            dst[j] = from < 0 ? static_cast<E>(marker_before(from)) : out[from];
+        }
+        return;
+    }
+    const E* src = dst - d;
+    uint32_t j = 0;
+    uint64_t w;
+    if (d >= W) {
+        if (d >= 4 * W) {
+            for (; j + 4 * W <= len; j += 4 * W) {
+                uint64_t x[4];
+                for (uint32_t k = 0; k < 4; ++k) __builtin_memcpy(&x[k], src + j + W * k, 8);
+                for (uint32_t k = 0; k < 4; ++k) __builtin_memcpy(dst + j + W * k, &x[k], 8);
+            }
+        }
+        for (; j + W <= len; j += W) {
+            __builtin_memcpy(&w, src + j, 8);
+            __builtin_memcpy(dst + j, &w, 8);
+        }
+        if (j < len) __builtin_memcpy(&w, src + j, 8);          // (ends at most where this match's own text begins)
+    } else {
+        __builtin_memcpy(&w, src, 8);                           // the d elements of the pattern and W - d that are not text yet
+        w &= ~0ull >> (64u - BITS * d);
+        for (uint32_t have = d; have < W; have <<= 1) w |= w << (BITS * have);
+        // the largest multiple of d within a word, (W / d) * d, spelled out: a division costs the device twenty instructions
+        const uint32_t step = W == 8 ? (d == 3 ? 6u : (d >= 5 ? d : 8u)) : (d == 3 ? 3u : 4u);
+        for (; j + W <= len; j += step) __builtin_memcpy(dst + j, &w, 8);
+    }
+    for (uint32_t k = 0; j + k < len; ++k) dst[j + k] = static_cast<E>(w >> (BITS * k));
+}
+
 // Inflates the raw DEFLATE stream in[0 .. in_len) into out[0 .. out_len): INFLATE_OK only if the stream is valid, ends
 // exactly at in_len and produces exactly out_len bytes.  in must be readable up to in_len + IN_SLACK.
 template<class Wave>
@@ -297,65 +499,15 @@ SCG_HD int inflate_member(const uint8_t* in, uint32_t in_len, uint8_t* out, uint
             continue;
         }
         if (type == 3) return INFLATE_BAD_DATA;                          // "invalid block type"
-        int nlen, ndist;
         if (type == 1) {
-            nlen = 288; ndist = 32;                                      // the fixed code (inflate.c: fixedtables)
-            for (int s = 0; s < 144; ++s) lens[s] = 8;
-            for (int s = 144; s < 256; ++s) lens[s] = 9;
-            for (int s = 256; s < 280; ++s) lens[s] = 7;
-            for (int s = 280; s < 288; ++s) lens[s] = 8;
-            for (int s = 0; s < 32; ++s) lens[288 + s] = 5;
-        } else {
-            nlen = static_cast<int>(br.bits(5)) + 257;
-            ndist = static_cast<int>(br.bits(5)) + 1;
-            const int ncode = static_cast<int>(br.bits(4)) + 4;
-            if (nlen > 286 || ndist > 30) return INFLATE_BAD_DATA;      // "too many length or distance symbols"
-            // the code-length code: its 19 lengths sit behind the 320 bytes reserved for the lengths proper
-            uint8_t* const cl = lens + 320;
-            const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-            for (int i = 0; i < 19; ++i) cl[i] = 0;
-            for (int i = 0; i < ncode; ++i) {
-                br.refill();
-                cl[order[i]] = static_cast<uint8_t>(br.bits(3));
-            }
-            // (its symbols and counts borrow the distance code's arrays, which are built afterwards)
-            if (!build_code(cl, 19, 0, T.dtab, DIST_BITS, T.dcount, T.dsym, T.offs)) return INFLATE_BAD_DATA;   // "invalid code lengths set"
-            int have = 0;
-            while (have < nlen + ndist) {
-                if (br.overrun()) return INFLATE_BAD_DATA;
-                br.refill();
-                const int s = decode_symbol(br, T.dtab, DIST_BITS, T.dcount, T.dsym);
-                if (s < 0) return INFLATE_BAD_DATA;
-                if (s < 16) {
-                    lens[have++] = static_cast<uint8_t>(s);
-                    continue;
-                }
-                uint8_t fill = 0;
-                int rep;
-                if (s == 16) {
-                    if (have == 0) return INFLATE_BAD_DATA;             // "invalid bit length repeat"
-                    fill = lens[have - 1];
-                    rep = 3 + static_cast<int>(br.bits(2));
-                } else if (s == 17) {
-                    rep = 3 + static_cast<int>(br.bits(3));
-                } else {
-                    rep = 11 + static_cast<int>(br.bits(7));
-                }
-                if (have + rep > nlen + ndist) return INFLATE_BAD_DATA;  // "invalid bit length repeat"
-                while (rep--) lens[have++] = fill;
-            }
-            if (lens[256] == 0) return INFLATE_BAD_DATA;                 // "invalid code -- missing end-of-block"
-        }
-        // distance code first: its lengths lie in the area the literal/length table is about to take
-        if (!build_code(lens + nlen, ndist, 1, T.dtab, DIST_BITS, T.dcount, T.dsym, T.offs)) return INFLATE_BAD_DATA;   // "invalid distances set"
-        {
-            // the literal/length table overwrites its own lengths: the builder reads them before it writes
-            if (!build_code(lens, nlen, 1, T.lit, LIT_BITS, T.lcount, T.lsym, T.offs)) return INFLATE_BAD_DATA;         // "invalid literal/lengths set"
+            if (!fixed_tables(T, lens)) return INFLATE_BAD_DATA;
+        } else if (!read_dynamic_tables(br, T, lens)) {
+            return INFLATE_BAD_DATA;
         }
         for (;;) {
             if (br.overrun()) return INFLATE_BAD_DATA;
             br.refill();
-            int s = decode_symbol(br, T.lit, LIT_BITS, T.lcount, T.lsym);
+            const int s = decode_symbol(br, T.lit, LIT_BITS, T.lcount, T.lsym);
             if (s < 0) return INFLATE_BAD_DATA;                          // "invalid literal/length code"
             if (s < 256) {
                 if (op >= out_len) return INFLATE_BAD_SIZE;
@@ -363,27 +515,8 @@ SCG_HD int inflate_member(const uint8_t* in, uint32_t in_len, uint8_t* out, uint
                 continue;
             }
             if (s == 256) break;
-            if (s > 285) return INFLATE_BAD_DATA;
-            s -= 257;
-            uint32_t n;
-            if (s < 8) {
-                n = static_cast<uint32_t>(s) + 3u;
-            } else if (s == 28) {
-                n = 258;
-            } else {
-                const uint32_t eb = static_cast<uint32_t>(s - 4) >> 2;
-                n = ((4u + (static_cast<uint32_t>(s) & 3u)) << eb) + 3u + br.bits(eb);
-            }
-            br.refill();
-            const int d = decode_symbol(br, T.dtab, DIST_BITS, T.dcount, T.dsym);
-            if (d < 0 || d >= 30) return INFLATE_BAD_DATA;               // "invalid distance code"
-            uint32_t dist;
-            if (d < 4) {
-                dist = static_cast<uint32_t>(d) + 1u;
-            } else {
-                const uint32_t eb = (static_cast<uint32_t>(d) >> 1) - 1u;
-                dist = ((2u + (static_cast<uint32_t>(d) & 1u)) << eb) + 1u + br.bits(eb);
-            }
+            uint32_t n, dist;
+            if (!read_match(br, T, s, n, dist)) return INFLATE_BAD_DATA;
             if (dist > op) return INFLATE_BAD_DATA;                      // "invalid distance too far back"
             if (n > out_len - op) return INFLATE_BAD_SIZE;
             w.match(n, dist);
@@ -394,6 +527,19 @@ SCG_HD int inflate_member(const uint8_t* in, uint32_t in_len, uint8_t* out, uint
     const uint32_t consumed = br.pos - (br.cnt >> 3);
     if (consumed != in_len || op != out_len) return INFLATE_BAD_SIZE;
     return INFLATE_OK;
+}
+
+// ---- CRC-32 of a text from the CRCs of its pieces ----
+// crc(A B) = crc(A) * x^(8 |B|) + crc(B) over GF(2) modulo the CRC polynomial (zlib's crc32_combine).
+// a * b mod p, reflected: bit 31 is x^0 (crc32.c: multmodp).
+SCG_HD uint32_t gf2_mult(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (int i = 0; i < 32 && a; ++i) {        // bit 31 of a first; done when no bits of a are left
+        if (a & 0x80000000u) p ^= b;
+        a <<= 1;
+        b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
+    }
+    return p;
 }
 
 }  // namespace scginf

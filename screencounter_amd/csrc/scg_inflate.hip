@@ -1,7 +1,10 @@
-// scg_inflate.hip -- BGZF members inflated on the device: one member per wavefront (scg_inflate.h), Huffman tables in LDS.
+// scg_inflate.hip -- BGZF members and ordinary gzip streams inflated on the device: one member or chunk per wavefront,
+// Huffman tables in LDS.  The rules of DEFLATE -- headers, tables, lengths and distances, a match's copy -- are
+// scg_inflate.h's, shared with the host tests; this file holds what is the device's own: how a wavefront's lanes share
+// the work (WaveLanes, the batches, chain walk and deferred matches of inflate_lanes), the kernels and their launchers.
 //
 // A window of a BGZF file is a few thousand independent gzip members of <= 64 KiB of text each.  Their compressed
-// bytes are shipped as they are (a fifth of the text), every wavefront of inflate_members_kernel decodes one member straight
+// bytes are shipped as they are (a fifth of the text), every wavefront of inflate_members_lanes_kernel decodes one member straight
 // into its place in the window's text buffer in HBM, crc_members_kernel checks every member's CRC-32 against its
 // trailer (one workgroup per member; the pieces are combined in GF(2) like zlib's crc32_combine), and the record scan
 // (scg_textscan.hip) runs on the text where it lies.  The host never sees the text: its threads -- sixteen zlib streams
@@ -21,6 +24,12 @@
 
 namespace {
 
+using scginf::MARKER;
+using scginf::MARKER_WINDOW;
+using scginf::WaveTables;
+using scginf::LANES_LIT_BITS;
+using scginf::LANES_DIST_BITS;
+
 // One wavefront per member.  DEFLATE decoding is a chain of dependent steps full of data-dependent branches: with one
 // member per LANE every lane that took a different path made the other 63 wait, and a window of 4 000 members took
 // 44 ms (1.5 MB/s per lane).  A wavefront that walks one member together keeps the decoder's state in scalar registers,
@@ -35,7 +44,7 @@ struct WaveLanes {
     __device__ __forceinline__ uint32_t width() const { return INFLATE_BLOCK; }
     __device__ __forceinline__ void set(Vec& v, uint32_t j, uint32_t byte) const { if (id == j) v = byte; }
     // j mod dist for this lane (dist is wave-uniform; matches that reach into their own output are the rare case)
-    __device__ __forceinline__ uint32_t wrap(uint32_t j, uint32_t n, uint32_t dist) const { return dist >= n ? j : (dist == 1 ? 0u : j % dist); }
+    static __device__ __forceinline__ uint32_t wrap(uint32_t j, uint32_t n, uint32_t dist) { return dist >= n ? j : (dist == 1 ? 0u : j % dist); }
     // The lanes hand bytes to one another through the text itself: what one lane stores, another may load a few symbols
     // later.  gfx9 issues a wavefront's vector memory operations in order, so that works as it stands; the
     // wavefront-scope fences (no instructions on this target) keep the COMPILER from moving a load of the text across
@@ -88,21 +97,11 @@ __global__ __launch_bounds__(INFLATE_BLOCK) void inflate_members_kernel(const ui
 // 66 -> 24 scalar and 35 -> 31 vector instructions per symbol; random-sequence reads 13.0 -> 6.4 ms.  (64 offsets a
 // batch: 3.9 / 6.8 ms; the per-symbol work -- one chain step, its share of 14 offsets' decoding -- is what is left.)
 // Codes longer than the primary tables, an end-of-block or an invalid pattern stop the chain; that one symbol is
-// decoded the old way (scginf::decode_symbol: canonical bit-by-bit decoding) and the batches go on behind it.
+// decoded the old way (scginf::decode_symbol: canonical bit-by-bit decoding; written in place with the header's length
+// and distance helpers: through read_match the compiler lays the whole kernel out anew) and the batches go on behind it.
 // Block headers (once per ~30 KB of text) are read by the wavefront as a whole, as before.  Accept / reject rules are
 // scg_inflate.h's; what this decoder gets wrong on a corrupt stream the CRC kernel catches, and zlib judges the file.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int LANES_LIT_BITS = 10, LANES_DIST_BITS = 8;      // (11 / 9 bits: no gain -- long codes are rare in FASTQ)
-struct WaveTables {                   // 3.3 KB of LDS per wavefront
-    uint16_t lit[1 << LANES_LIT_BITS];
-    uint16_t dtab[1 << LANES_DIST_BITS];
-    uint16_t lsym[288];
-    uint16_t dsym[32];
-    uint16_t lcount[16];
-    uint16_t dcount[16];
-    uint16_t offs[16];
-};
-
 // What a wavefront keeps next to its tables (2 KB): a ring of the compressed bytes around the read position, so that a
 // batch's 64 overlapping 8-byte reads come from LDS and the stream is fetched from HBM 512 bytes at a time, one fetch
 // ahead of its use; and the matches that have been decoded but not copied yet (see resolve_matches).
@@ -166,80 +165,6 @@ struct InRing {
     }
 };
 
-// The decoder writes bytes (BGZF members: the text itself) or 16-bit symbols (chunks of an ordinary gzip stream, decoded
-// without the 32 KiB of text in front of them: a symbol is a byte, or MARKER + k for "byte k of the window I do not have";
-// scg_pgzip.h).  In symbol mode a match may reach in front of the chunk's first symbol: those positions read as markers.
-constexpr uint32_t MARKER = 0x8000u, MARKER_WINDOW = 32768u;
-
-// One match, copied by one lane.  A source at least 8 bytes back is moved in 8-byte words (up to four loads in flight);
-// a closer one is a pattern of period `d`, built once in a register and stored over and over.
-__device__ __forceinline__ void copy_match(uint8_t* out, uint32_t at, uint32_t len, uint32_t d) {
-    uint8_t* dst = out + at;
-    const uint8_t* src = dst - d;
-    uint32_t j = 0;
-    uint64_t w;
-    if (d >= 8) {
-        if (d >= 32) {
-            for (; j + 32 <= len; j += 32) {
-                uint64_t x[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) __builtin_memcpy(&x[k], src + j + 8 * k, 8);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) __builtin_memcpy(dst + j + 8 * k, &x[k], 8);
-            }
-        }
-        for (; j + 8 <= len; j += 8) {
-            __builtin_memcpy(&w, src + j, 8);
-            __builtin_memcpy(dst + j, &w, 8);
-        }
-        if (j < len) __builtin_memcpy(&w, src + j, 8);          // (ends at most where this match's own text begins)
-    } else {
-        __builtin_memcpy(&w, src, 8);                           // the d bytes of the pattern and 8 - d that are not text yet
-        w &= ~0ull >> (64u - 8u * d);
-        for (uint32_t have = d; have < 8; have <<= 1) w |= w << (8u * have);
-        const uint32_t step = d == 3 ? 6u : (d >= 5 ? d : 8u);  // the largest multiple of d within a word
-        for (; j + 8 <= len; j += step) __builtin_memcpy(dst + j, &w, 8);
-    }
-    for (uint32_t k = 0; j + k < len; ++k) dst[j + k] = static_cast<uint8_t>(w >> (8u * k));
-}
-// The same in symbols (four to a word); a match that begins in front of the chunk goes symbol by symbol.
-__device__ __forceinline__ void copy_match(uint16_t* out, uint32_t at, uint32_t len, uint32_t d) {
-    uint16_t* dst = out + at;
-    if (at < d) {
-        for (uint32_t j = 0; j < len; ++j) {
-            const int32_t from = static_cast<int32_t>(at + j) - static_cast<int32_t>(d);
-            dst[j] = from < 0 ? static_cast<uint16_t>(MARKER + MARKER_WINDOW + from) : out[from];
-        }
-        return;
-    }
-    const uint16_t* src = dst - d;
-    uint32_t j = 0;
-    uint64_t w;
-    if (d >= 4) {
-        if (d >= 16) {
-            for (; j + 16 <= len; j += 16) {
-                uint64_t x[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) __builtin_memcpy(&x[k], src + j + 4 * k, 8);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) __builtin_memcpy(dst + j + 4 * k, &x[k], 8);
-            }
-        }
-        for (; j + 4 <= len; j += 4) {
-            __builtin_memcpy(&w, src + j, 8);
-            __builtin_memcpy(dst + j, &w, 8);
-        }
-        if (j < len) __builtin_memcpy(&w, src + j, 8);
-    } else {
-        __builtin_memcpy(&w, src, 8);
-        w &= ~0ull >> (64u - 16u * d);
-        for (uint32_t have = d; have < 4; have <<= 1) w |= w << (16u * have);
-        const uint32_t step = d == 3 ? 3u : 4u;
-        for (; j + 4 <= len; j += step) __builtin_memcpy(dst + j, &w, 8);
-    }
-    for (uint32_t k = 0; j + k < len; ++k) dst[j + k] = static_cast<uint16_t>(w >> (16u * k));
-}
-
 // Copies the nm matches of S.tok_* in rounds of up to 64, one match per lane.  A match may go when everything it reads
 // is final: the text in front of the earliest match that has not been copied yet (all literals are in place already,
 // and matches before that one are done).  The earliest pending match always goes (it reads only text in front of
@@ -260,7 +185,7 @@ __device__ __forceinline__ void resolve_matches(OutT* out, const WaveStage& S, u
             const uint32_t first = static_cast<uint32_t>(__builtin_ctzll(pending));
             const uint32_t final_to = rdlane(at, first);
             const bool go = ((pending >> lane) & 1ull) && (src_end <= static_cast<int32_t>(final_to) || lane == first);
-            if (go) copy_match(out, at, len, d);
+            if (go) scginf::copy_match(out, at, len, d);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             pending &= ~ballot64(go);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -273,9 +198,8 @@ template<class OutT>
 __device__ __forceinline__ void wave_copy(OutT* out, uint32_t at, uint32_t n, uint32_t dist, uint32_t lane) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     for (uint32_t j = lane; j < n; j += INFLATE_BLOCK) {
-        const uint32_t k = dist >= n ? j : (dist == 1 ? 0u : j % dist);
-        const int32_t from = static_cast<int32_t>(at + k) - static_cast<int32_t>(dist);
-        out[at + j] = (sizeof(OutT) == 2 && from < 0) ? static_cast<OutT>(MARKER + MARKER_WINDOW + from) : out[from];
+        const int32_t from = static_cast<int32_t>(at + WaveLanes::wrap(j, n, dist)) - static_cast<int32_t>(dist);
+        out[at + j] = (sizeof(OutT) == 2 && from < 0) ? static_cast<OutT>(scginf::marker_before(from)) : out[from];
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 }
@@ -284,88 +208,6 @@ template<class OutT>
 __device__ __forceinline__ void wave_store(OutT* out, uint32_t at, const uint8_t* src, uint32_t n, uint32_t lane) {
     for (uint32_t j = lane; j < n; j += INFLATE_BLOCK) out[at + j] = src[j];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-}
-
-// What the code starting at the low end of `w` would be (>= 57 valid bits), were it a code start.
-// kind: 0 literal, 1 match, 2 end of block, 3 "not decodable here" (long code / invalid: the chain stops)
-struct LaneCode {
-    uint32_t kind, adv, outlen, n, dist, sym;
-};
-__device__ __forceinline__ LaneCode decode_here(const WaveTables& T, uint64_t w) {
-    // Straight-line: every lane goes through the length and the distance arithmetic, whatever its code is, and the
-    // results are selected at the end.  As nested branches this cost 13 exec-mask save / restore pairs and 40 register
-    // moves per 64 offsets -- scalar instructions the whole wavefront waits for, most of them for offsets that are no code
-    // starts anyway.
-    LaneCode c;
-    const uint32_t e = T.lit[static_cast<uint32_t>(w) & ((1u << LANES_LIT_BITS) - 1u)];
-    const uint32_t l = e >> 12;
-    c.sym = e & 0xFFFu;
-    const uint32_t t0 = c.sym - 257u;                                   // (wraps for literals: clamped, and not used then)
-    const uint32_t t = t0 < 28u ? t0 : 28u;
-    const bool plain = t < 8u || t == 28u;
-    const uint32_t eb = plain ? 0u : (t - 4u) >> 2;
-    const uint32_t base = t < 8u ? t + 3u : (t == 28u ? 258u : ((4u + (t & 3u)) << eb) + 3u);
-    uint64_t w2 = w >> l;
-    c.n = base + (static_cast<uint32_t>(w2) & ((1u << eb) - 1u));
-    w2 >>= eb;
-    const uint32_t de = T.dtab[static_cast<uint32_t>(w2) & ((1u << LANES_DIST_BITS) - 1u)];
-    const uint32_t dl = de >> 12, ds0 = de & 0xFFFu;
-    const uint32_t ds = ds0 < 29u ? ds0 : 29u;
-    const uint32_t deb = ds < 4u ? 0u : (ds >> 1) - 1u;
-    const uint32_t dbase = ds < 4u ? ds + 1u : ((2u + (ds & 1u)) << deb) + 1u;
-    w2 >>= dl;
-    c.dist = dbase + (static_cast<uint32_t>(w2) & ((1u << deb) - 1u));
-    const bool is_length = c.sym > 256u && c.sym <= 285u;
-    const bool is_match = is_length && de != 0u && ds0 < 30u;
-    c.kind = e == 0u ? 3u : (c.sym < 256u ? 0u : (c.sym == 256u ? 2u : (is_match ? 1u : 3u)));
-    c.adv = c.kind == 1u ? l + eb + dl + deb : l;
-    c.outlen = c.kind == 0u ? 1u : (c.kind == 1u ? c.n : 0u);
-    return c;
-}
-
-// The code lengths of a dynamic-Huffman block header (br stands behind BFINAL and BTYPE) and the block's two tables.
-// False for anything zlib would reject (too many codes, an over-subscribed or incomplete set, no end-of-block code).
-__device__ __forceinline__ bool read_dynamic_tables(scginf::BitReader& br, WaveTables& T, uint8_t* lens) {
-    using namespace scginf;
-    const int nlen = static_cast<int>(br.bits(5)) + 257;
-    const int ndist = static_cast<int>(br.bits(5)) + 1;
-    const int ncode = static_cast<int>(br.bits(4)) + 4;
-    if (nlen > 286 || ndist > 30) return false;
-    uint8_t* const cl = lens + 320;
-    // the order of the code-length code's lengths (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15), five bits each
-    const uint64_t order_lo = 0x22caa324e804a30ull, order_hi = 0x3c2e1346cull;
-    for (int i = 0; i < 19; ++i) cl[i] = 0;
-    for (int i = 0; i < ncode; ++i) {
-        br.refill();
-        const uint32_t at = static_cast<uint32_t>((i < 12 ? order_lo >> (5 * i) : order_hi >> (5 * (i - 12))) & 31u);
-        cl[at] = static_cast<uint8_t>(br.bits(3));
-    }
-    if (!build_code(cl, 19, 0, T.dtab, 7, T.dcount, T.dsym, T.offs)) return false;
-    int have = 0;
-    while (have < nlen + ndist) {
-        if (br.overrun()) return false;
-        br.refill();
-        const int s = decode_symbol(br, T.dtab, 7, T.dcount, T.dsym);
-        if (s < 0) return false;
-        if (s < 16) { lens[have++] = static_cast<uint8_t>(s); continue; }
-        uint8_t fill = 0;
-        int rep;
-        if (s == 16) {
-            if (have == 0) return false;
-            fill = lens[have - 1];
-            rep = 3 + static_cast<int>(br.bits(2));
-        } else if (s == 17) {
-            rep = 3 + static_cast<int>(br.bits(3));
-        } else {
-            rep = 11 + static_cast<int>(br.bits(7));
-        }
-        if (have + rep > nlen + ndist) return false;
-        while (rep--) lens[have++] = fill;
-    }
-    if (lens[256] == 0) return false;
-    if (!build_code(lens + nlen, ndist, 1, T.dtab, LANES_DIST_BITS, T.dcount, T.dsym, T.offs)) return false;
-    if (!build_code(lens, nlen, 1, T.lit, LANES_LIT_BITS, T.lcount, T.lsym, T.offs)) return false;
-    return true;
 }
 
 // Decodes DEFLATE blocks from bit `start_bit` of in[0 .. in_len) until a final block ends or a block ends at or beyond
@@ -390,11 +232,7 @@ __device__ __forceinline__ int inflate_lanes(const uint8_t* __restrict__ in, uin
         if (bitpos > in_bits) return INFLATE_BAD_DATA;
         // ---- block header: the wavefront as a whole ----
         BitReader br;
-        br.open(in, in_len);
-        br.seek(bitpos >> 3);
-        br.refill();
-        br.bits(bitpos & 7u);
-        br.refill();
+        br.open_at_bit(in, in_len, bitpos);
         last = br.bits(1);
         const uint32_t type = br.bits(2);
         if (type == 0) {
@@ -415,17 +253,11 @@ __device__ __forceinline__ int inflate_lanes(const uint8_t* __restrict__ in, uin
         }
         if (type == 3) return INFLATE_BAD_DATA;
         if (type == 1) {
-            for (int s = 0; s < 144; ++s) lens[s] = 8;
-            for (int s = 144; s < 256; ++s) lens[s] = 9;
-            for (int s = 256; s < 280; ++s) lens[s] = 7;
-            for (int s = 280; s < 288; ++s) lens[s] = 8;
-            for (int s = 0; s < 32; ++s) lens[288 + s] = 5;
-            if (!build_code(lens + 288, 32, 1, T.dtab, LANES_DIST_BITS, T.dcount, T.dsym, T.offs)) return INFLATE_BAD_DATA;
-            if (!build_code(lens, 288, 1, T.lit, LANES_LIT_BITS, T.lcount, T.lsym, T.offs)) return INFLATE_BAD_DATA;
+            if (!fixed_tables(T, lens)) return INFLATE_BAD_DATA;
         } else if (!read_dynamic_tables(br, T, lens)) {
             return INFLATE_BAD_DATA;
         }
-        bitpos = (br.pos * 8u) - br.cnt;
+        bitpos = br.bit_position();
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");          // the tables, written through one lane's eyes, are read per lane below
 
         // ---- the block's symbols, 64 bit offsets at a time ----
@@ -512,12 +344,8 @@ __device__ __forceinline__ int inflate_lanes(const uint8_t* __restrict__ in, uin
             }
             // one symbol the old way: a code longer than the primary tables, or an error to be named
             BitReader sr;
-            sr.open(in, in_len);
-            sr.seek(bitpos >> 3);
-            sr.refill();
-            sr.bits(bitpos & 7u);
-            sr.refill();
-            int s = decode_symbol(sr, T.lit, LANES_LIT_BITS, T.lcount, T.lsym);
+            sr.open_at_bit(in, in_len, bitpos);
+            const int s = decode_symbol(sr, T.lit, LANES_LIT_BITS, T.lcount, T.lsym);
             if (s < 0) return INFLATE_BAD_DATA;
             if (s < 256) {
                 if (op >= out_len) return INFLATE_BAD_SIZE;
@@ -528,23 +356,13 @@ __device__ __forceinline__ int inflate_lanes(const uint8_t* __restrict__ in, uin
                 block_done = true;
             } else {
                 if (s > 285) return INFLATE_BAD_DATA;
-                s -= 257;
-                uint32_t len;
-                if (s < 8) len = static_cast<uint32_t>(s) + 3u;
-                else if (s == 28) len = 258;
-                else {
-                    const uint32_t eb = static_cast<uint32_t>(s - 4) >> 2;
-                    len = ((4u + (static_cast<uint32_t>(s) & 3u)) << eb) + 3u + sr.bits(eb);
-                }
+                const uint32_t lt = static_cast<uint32_t>(s) - 257u, leb = length_extra(lt);
+                const uint32_t len = length_base(lt, leb) + sr.bits(leb);
                 sr.refill();
                 const int dcode = decode_symbol(sr, T.dtab, LANES_DIST_BITS, T.dcount, T.dsym);
                 if (dcode < 0 || dcode >= 30) return INFLATE_BAD_DATA;
-                uint32_t d;
-                if (dcode < 4) d = static_cast<uint32_t>(dcode) + 1u;
-                else {
-                    const uint32_t eb = (static_cast<uint32_t>(dcode) >> 1) - 1u;
-                    d = ((2u + (static_cast<uint32_t>(dcode) & 1u)) << eb) + 1u + sr.bits(eb);
-                }
+                const uint32_t deb = dist_extra(static_cast<uint32_t>(dcode));
+                const uint32_t d = dist_base(static_cast<uint32_t>(dcode), deb) + sr.bits(deb);
                 if (!SYMBOLS && d > op) return INFLATE_BAD_DATA;
                 if (len > out_len - op) return INFLATE_BAD_SIZE;
                 resolve_matches(out, S, nm, lane);                       // (its source may be one of them)
@@ -552,7 +370,7 @@ __device__ __forceinline__ int inflate_lanes(const uint8_t* __restrict__ in, uin
                 wave_copy(out, op, len, d, lane);
                 op += len;
             }
-            bitpos = (sr.pos * 8u) - sr.cnt;
+            bitpos = sr.bit_position();
         }
     } while (!last && bitpos < stop_bit);
     resolve_matches(out, S, nm, lane);
@@ -571,7 +389,8 @@ __device__ __forceinline__ int inflate_member_lanes(const uint8_t* __restrict__ 
 }
 
 #ifndef SCG_INFLATE_WAVES
-#define SCG_INFLATE_WAVES 7          /* 72 VGPRs, no spills (8 = 64 VGPRs spills 9 dwords; A/B within noise) */
+#define SCG_INFLATE_WAVES 7          /* waves per SIMD: a budget of 72 VGPRs (8 = 64 VGPRs: A/B within noise).  Either way the
+                                        compiler spills some dwords to scratch; tools/kernel_resources.sh reports how many */
 #endif
 __global__ __launch_bounds__(INFLATE_BLOCK, SCG_INFLATE_WAVES) void inflate_members_lanes_kernel(const uint8_t* __restrict__ in, const scg::InflateMember* __restrict__ members,
                                                                               uint32_t n, uint8_t* text, uint32_t* __restrict__ status) {
@@ -598,7 +417,20 @@ __global__ __launch_bounds__(INFLATE_BLOCK, SCG_INFLATE_WAVES) void inflate_memb
 //                          markers point into the 32 KiB before the chunk, which are text by then);
 //   gunzip_resolve_kernel  everything else becomes text, all chunks at once.
 // ---------------------------------------------------------------------------------------------------------------
-// `in` holds the file's bytes [origin, size); chunks[k] is chunk number chunk0 + k of the stream (a group of a long file).
+// `in_slice` holds the file's bytes [origin, size); chunks[k] is chunk number chunk0 + k of the stream (a group of a long file).
+
+// The file from bit `at` (a position in the whole file, >= origin * 8) on, as the decoders take their input: from the
+// byte that holds that bit, which keeps positions in 32 bits.
+struct FileView {
+    const uint8_t* in;
+    uint32_t in_len, bit;              // bytes up to the file's end (2^28 at the most); the bit's place in in[0]
+    uint64_t bit0;                     // file position of in[0]'s first bit
+};
+__device__ __forceinline__ FileView view_from(const uint8_t* __restrict__ in_slice, uint64_t origin, uint64_t size, uint64_t at) {
+    const uint64_t byte0 = at >> 3, left = size - byte0;
+    return FileView{in_slice - origin + byte0, static_cast<uint32_t>(left < (1u << 28) ? left : (1u << 28)), static_cast<uint32_t>(at & 7u), byte0 * 8u};
+}
+
 __global__ __launch_bounds__(INFLATE_BLOCK) void gunzip_find_kernel(const uint8_t* __restrict__ in_slice, uint64_t origin, uint64_t size,
                                                                     scg::GunzipChunk* __restrict__ chunks, uint32_t n, uint64_t chunk0, uint64_t first_byte,
                                                                     uint64_t chunk_bytes, uint64_t stream_end_byte) {
@@ -637,14 +469,11 @@ __global__ __launch_bounds__(INFLATE_BLOCK) void gunzip_find_kernel(const uint8_
             const uint32_t k = static_cast<uint32_t>(__builtin_ctzll(cand));
             cand &= cand - 1;
             const uint64_t at = base + k;
-            // the header in full, by the wavefront as a whole: relative to a base that keeps positions in 32 bits
-            const uint64_t byte0 = at >> 3;
-            const uint64_t left = size - byte0;
+            // the header in full, by the wavefront as a whole
+            const FileView f = view_from(in_slice, origin, size, at);
             BitReader br;
-            br.open(in + byte0, static_cast<uint32_t>(left < (1u << 28) ? left : (1u << 28)));
-            br.refill();
-            br.bits(static_cast<uint32_t>(at & 7u) + 3u);               // BFINAL, BTYPE
-            br.refill();
+            br.open_at_bit(f.in, f.in_len, f.bit);
+            br.bits(3);                                                 // BFINAL, BTYPE
             if (read_dynamic_tables(br, tables, lens) && !br.overrun()) { found = at; break; }
         }
     }
@@ -658,7 +487,6 @@ __global__ __launch_bounds__(INFLATE_BLOCK, SCG_INFLATE_WAVES) void gunzip_decod
                                                                                         uint16_t* __restrict__ syms, uint64_t cap_syms) {
     __shared__ WaveTables tables;
     __shared__ WaveStage stage;
-    const uint8_t* in = in_slice - origin;
     const uint32_t c = blockIdx.x;
     if (c >= n_decode) return;
     const uint64_t start = chunks[c].start_bit;
@@ -671,18 +499,16 @@ __global__ __launch_bounds__(INFLATE_BLOCK, SCG_INFLATE_WAVES) void gunzip_decod
         const uint64_t s = chunks[k].start_bit;
         if (s != ~0ull) { stop = s; break; }
     }
-    const uint64_t byte0 = start >> 3;
-    const uint64_t left = size - byte0;
-    const uint32_t in_len = static_cast<uint32_t>(left < (1u << 28) ? left : (1u << 28));
-    const uint64_t rel_stop = stop == ~0ull ? ~0ull : stop - byte0 * 8u;
+    const FileView f = view_from(in_slice, origin, size, start);
+    const uint64_t rel_stop = stop == ~0ull ? ~0ull : stop - f.bit0;
     LanesResult r;
     r.end_bit = 0; r.made = 0; r.final_block = 0;
-    const int rc = inflate_lanes<uint16_t>(in + byte0, in_len, static_cast<uint32_t>(start & 7u), rel_stop < 0x7FFFFFFFull ? static_cast<uint32_t>(rel_stop) : 0x7FFFFFFFu,
+    const int rc = inflate_lanes<uint16_t>(f.in, f.in_len, f.bit, rel_stop < 0x7FFFFFFFull ? static_cast<uint32_t>(rel_stop) : 0x7FFFFFFFu,
                                            syms + cap_syms * c, static_cast<uint32_t>(cap_syms), tables, stage, threadIdx.x, r);
     if (threadIdx.x == 0) {
         chunks[c].status = static_cast<uint32_t>(rc);
         chunks[c].made = r.made;
-        chunks[c].end_bit = byte0 * 8u + r.end_bit;
+        chunks[c].end_bit = f.bit0 + r.end_bit;
         chunks[c].final_block = r.final_block;
     }
 }
@@ -705,6 +531,18 @@ __device__ __forceinline__ uint32_t group_made(const scg::GunzipChunk* __restric
     uint64_t sum = 0;
     for (uint32_t c = c0; c < c1; ++c) sum += chunks[c].made;
     return static_cast<uint32_t>(sum < MARKER_WINDOW ? sum : MARKER_WINDOW);
+}
+
+// A symbol as text: a byte is itself, MARKER + w is byte w of the window in front of its chunk.  win[first_valid ..) is
+// what of that window belongs to the member; a reference in front of it (in front of the stream) reads as 0 and sets `bad`.
+__device__ __forceinline__ uint8_t text_byte(uint32_t x, const uint8_t* win, uint32_t first_valid, bool& bad) {
+    uint8_t byte = static_cast<uint8_t>(x);
+    if (x >= MARKER) {
+        const uint32_t w = x - MARKER;
+        if (w >= first_valid) byte = win[w];
+        else { bad = true; byte = 0; }
+    }
+    return byte;
 }
 
 __global__ __launch_bounds__(TAILS_BLOCK) void gunzip_tail_maps_kernel(const uint16_t* __restrict__ syms, uint64_t cap_syms, const scg::GunzipChunk* __restrict__ chunks,
@@ -795,12 +633,7 @@ __global__ __launch_bounds__(TAILS_BLOCK) void gunzip_tails_kernel(const uint16_
             for (int k = 0; k < PER; ++k) v[k] = s[threadIdx.x + k * TAILS_BLOCK];
 #pragma unroll
             for (int k = 0; k < PER; ++k) {
-                uint8_t byte = static_cast<uint8_t>(v[k]);
-                if (v[k] >= MARKER) {
-                    const uint32_t w = v[k] - MARKER;
-                    if (w >= first_valid) byte = win[cur][w];
-                    else { bad = true; byte = 0; }                       // (a reference in front of the stream)
-                }
+                const uint8_t byte = text_byte(v[k], win[cur], first_valid, bad);
                 win[cur ^ 1][threadIdx.x + k * TAILS_BLOCK] = byte;
                 t[threadIdx.x + k * TAILS_BLOCK] = byte;
             }
@@ -812,13 +645,7 @@ __global__ __launch_bounds__(TAILS_BLOCK) void gunzip_tails_kernel(const uint16_
             const uint32_t keep = MARKER_WINDOW - made;
             for (uint32_t i = threadIdx.x; i < keep; i += TAILS_BLOCK) win[cur ^ 1][i] = win[cur][i + made];
             for (uint32_t i = threadIdx.x; i < made; i += TAILS_BLOCK) {
-                const uint32_t x = s[i];
-                uint8_t byte = static_cast<uint8_t>(x);
-                if (x >= MARKER) {
-                    const uint32_t w = x - MARKER;
-                    if (w >= first_valid) byte = win[cur][w];
-                    else { bad = true; byte = 0; }
-                }
+                const uint8_t byte = text_byte(s[i], win[cur], first_valid, bad);
                 win[cur ^ 1][keep + i] = byte;
                 t[i] = byte;
             }
@@ -865,13 +692,6 @@ __global__ __launch_bounds__(RESOLVE_BLOCK) void gunzip_resolve_kernel(const uin
     const uint32_t ga = static_cast<uint32_t>(static_cast<uint64_t>(groups) * slice / RESOLVE_SLICES);
     const uint32_t gb = static_cast<uint32_t>(static_cast<uint64_t>(groups) * (slice + 1) / RESOLVE_SLICES);
     bool bad = false;
-    auto byte_of = [&](uint32_t x) -> uint32_t {
-        if (x < MARKER) return x & 0xFFu;
-        const uint32_t w = x - MARKER;
-        if (w >= first_valid) return win[w];
-        bad = true;
-        return 0u;
-    };
     for (uint32_t g = ga + threadIdx.x; g < gb; g += RESOLVE_BLOCK) {
         const uint32_t i = g << 3;
         if (i + 8u <= body) {
@@ -880,26 +700,15 @@ __global__ __launch_bounds__(RESOLVE_BLOCK) void gunzip_resolve_kernel(const uin
             uint64_t out = 0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                out |= static_cast<uint64_t>(byte_of(q[k] & 0xFFFFu)) << (16 * k);
-                out |= static_cast<uint64_t>(byte_of(q[k] >> 16)) << (16 * k + 8);
+                out |= static_cast<uint64_t>(text_byte(q[k] & 0xFFFFu, win, first_valid, bad)) << (16 * k);
+                out |= static_cast<uint64_t>(text_byte(q[k] >> 16, win, first_valid, bad)) << (16 * k + 8);
             }
             __builtin_memcpy(t + i, &out, 8);
         } else {
-            for (uint32_t j = i; j < body; ++j) t[j] = static_cast<uint8_t>(byte_of(s[j]));   // (the tail behind is text already)
+            for (uint32_t j = i; j < body; ++j) t[j] = text_byte(s[j], win, first_valid, bad);   // (the tail behind is text already)
         }
     }
     if (bad) atomicOr(status, 1u);
-}
-
-// zlib's crc32.c: a * b mod p over GF(2), reflected (bit 31 is x^0).
-__device__ __forceinline__ uint32_t multmodp(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (int i = 0; i < 32 && a; ++i) {        // bit 31 of a first; done when no bits of a are left
-        if (a & 0x80000000u) p ^= b;
-        a <<= 1;
-        b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-    }
-    return p;
 }
 
 constexpr int CRC_BLOCK = 256;
@@ -940,8 +749,8 @@ __global__ __launch_bounds__(CRC_BLOCK) void crc_members_kernel(const uint8_t* _
         c = (b > a) ? ~c : 0u;                                 // (the CRC of nothing is 0)
         // x^(8 * (out_len - b)): product of the precomputed x^(2^k) over the set bits of the exponent
         uint32_t behind = M.out_len - b, x = 1u << 31;
-        for (int k = 3; behind; ++k, behind >>= 1) if (behind & 1u) x = multmodp(P.x2n[k & 31], x);
-        c = c ? multmodp(x, c) : 0u;
+        for (int k = 3; behind; ++k, behind >>= 1) if (behind & 1u) x = scginf::gf2_mult(P.x2n[k & 31], x);
+        c = c ? scginf::gf2_mult(x, c) : 0u;
         for (int off = 32; off > 0; off >>= 1) c ^= __shfl_down(c, off, 64);
         if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
         __syncthreads();
@@ -988,22 +797,10 @@ size_t inflate_input_slack() { return scginf::IN_SLACK; }
 
 const CrcPowers& crc_powers() {
     static const CrcPowers P = [] {
-        auto mult = [](uint32_t a, uint32_t b) {
-            uint32_t m = 1u << 31, p = 0;
-            for (;;) {
-                if (a & m) {
-                    p ^= b;
-                    if ((a & (m - 1)) == 0) break;
-                }
-                m >>= 1;
-                b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-            }
-            return p;
-        };
         CrcPowers t;
         uint32_t p = 1u << 30;                 // x^1
         t.x2n[0] = p;
-        for (int k = 1; k < 32; ++k) t.x2n[k] = p = mult(p, p);
+        for (int k = 1; k < 32; ++k) t.x2n[k] = p = scginf::gf2_mult(p, p);
         return t;
     }();
     return P;

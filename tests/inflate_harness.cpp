@@ -1,5 +1,6 @@
-// inflate_harness.cpp -- host-side differential test of csrc/scg_inflate.h (the per-lane DEFLATE decoder of the device
-// inflate kernel) against zlib.  Built by tests/test_inflate_cpu.py with g++ -fsanitize=address,undefined.
+// inflate_harness.cpp -- host-side differential test of csrc/scg_inflate.h (the DEFLATE rules of the device inflate
+// kernels) against zlib: the per-wavefront decoder as it is, and a model of the lane-parallel decoder built from the
+// functions that decoder shares with it.  Built by tests/test_inflate_cpu.py with g++ -fsanitize=address,undefined.
 //   inflate_harness <seed> <rounds>
 //   inflate_harness --streams FILE
 // Valid streams of many shapes (levels 0-9, Z_FIXED / Z_HUFFMAN_ONLY / Z_RLE / Z_FILTERED, FASTQ-like, random, runs)
@@ -12,6 +13,8 @@
 
 #include <zlib.h>
 
+#include <algorithm>
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -92,8 +95,90 @@ static bool zlib_inflate(const std::vector<uint8_t>& c, size_t n, std::vector<ui
     return ok;
 }
 
+// The lane-parallel decoder's arithmetic without its scheduling (scg_inflate.hip: inflate_lanes / inflate_member_lanes):
+// the same tables, and at every code start decode_here on the 64 bits found there -- the device does that for 128 bit
+// offsets at once and then walks the chain of true code starts; here the chain is walked one start at a time, and a
+// match is copied at once (copy_match) where the device defers it.  What decode_here does not resolve (kind 3) takes
+// the bitwise path, as on the device.  OutT = uint8_t: a BGZF member's text; uint16_t: symbols, with nothing in front.
+constexpr size_t COPY_SLACK = 8;        // bytes behind the output that copy_match may read (scg_inflate.h)
+template<class OutT>
+static int lanes_model(const uint8_t* in, uint32_t in_len, OutT* out, uint32_t out_len) {
+    using namespace scginf;
+    static WaveTables T;
+    uint32_t bitpos = 0, op = 0, last;
+    const uint32_t in_bits = in_len * 8u;
+    do {
+        if (bitpos > in_bits) return INFLATE_BAD_DATA;
+        BitReader br;
+        br.open_at_bit(in, in_len, bitpos);
+        last = br.bits(1);
+        const uint32_t type = br.bits(2);
+        if (type == 0) {
+            br.bits(br.cnt & 7u);
+            br.refill();
+            br.refill();
+            const uint32_t n = br.bits(16), nn = br.bits(16);
+            if ((n ^ 0xFFFFu) != nn) return INFLATE_BAD_DATA;
+            if (n > out_len - op) return INFLATE_BAD_SIZE;
+            const uint32_t from = br.pos - (br.cnt >> 3);
+            if (from > in_len || n > in_len - from) return INFLATE_BAD_DATA;
+            for (uint32_t j = 0; j < n; ++j) out[op + j] = in[from + j];
+            op += n;
+            bitpos = (from + n) * 8u;
+            continue;
+        }
+        if (type == 3) return INFLATE_BAD_DATA;
+        uint8_t* const lens = reinterpret_cast<uint8_t*>(T.lit);
+        if (!(type == 1 ? fixed_tables(T, lens) : read_dynamic_tables(br, T, lens))) return INFLATE_BAD_DATA;
+        bitpos = br.bit_position();
+        for (bool block_done = false; !block_done;) {
+            if (bitpos > in_bits) return INFLATE_BAD_DATA;
+            uint64_t w;                                                  // (the device's ring reads zeros beyond in_len + IN_SLACK)
+            memcpy(&w, in + (bitpos >> 3), 8);
+            const LaneCode c = decode_here(T, w >> (bitpos & 7u));
+            if (c.kind == 0) {
+                if (op >= out_len) return INFLATE_BAD_SIZE;
+                out[op++] = static_cast<OutT>(c.sym);
+                bitpos += c.adv;
+            } else if (c.kind == 1) {
+                if (sizeof(OutT) == 1 && c.dist > op) return INFLATE_BAD_DATA;
+                if (c.n > out_len - op) return INFLATE_BAD_SIZE;
+                copy_match(out, op, c.n, c.dist);
+                op += c.n;
+                bitpos += c.adv;
+            } else if (c.kind == 2) {
+                bitpos += c.adv;
+                block_done = true;
+            } else {
+                BitReader sr;
+                sr.open_at_bit(in, in_len, bitpos);
+                const int s = decode_symbol(sr, T.lit, LANES_LIT_BITS, T.lcount, T.lsym);
+                if (s < 0) return INFLATE_BAD_DATA;
+                if (s < 256) {
+                    if (op >= out_len) return INFLATE_BAD_SIZE;
+                    out[op++] = static_cast<OutT>(s);
+                } else if (s == 256) {
+                    block_done = true;
+                } else {
+                    uint32_t len, d;
+                    if (!read_match(sr, T, s, len, d)) return INFLATE_BAD_DATA;
+                    if (sizeof(OutT) == 1 && d > op) return INFLATE_BAD_DATA;
+                    if (len > out_len - op) return INFLATE_BAD_SIZE;
+                    copy_match(out, op, len, d);
+                    op += len;
+                }
+                bitpos = sr.bit_position();
+            }
+        }
+    } while (!last);
+    if (((bitpos + 7u) >> 3) != in_len || op != out_len) return INFLATE_BAD_SIZE;
+    return INFLATE_OK;
+}
+
 // The decoder with "wavefronts" of 1, 7 and 64 lanes (the device runs 64): all must agree, byte for byte and verdict
-// for verdict -- the wider ones exercise the batched literals and the deferred stores of short matches.
+// for verdict -- the wider ones exercise the batched literals and the deferred stores of short matches.  So must the model
+// of the lane-parallel decoder, in bytes and -- whatever is accepted -- in symbols, where no marker may appear: nothing
+// reaches in front of a member's start.
 static int ours(const std::vector<uint8_t>& c, size_t n, std::vector<uint8_t>& out) {
     // exact-size buffers so that ASan sees any access beyond the slack or the output
     std::vector<uint8_t> in(c.size() + scginf::IN_SLACK, 0xA5);
@@ -109,6 +194,23 @@ static int ours(const std::vector<uint8_t>& c, size_t n, std::vector<uint8_t>& o
     if ((rc1 == scginf::INFLATE_OK) != ok || (rc7 == scginf::INFLATE_OK) != ok || (ok && (o1 != out || o7 != out))) {
         fprintf(stderr, "FAIL the lane widths disagree: rc %d / %d / %d\n", rc, rc1, rc7);
         exit(1);
+    }
+    // exact-size buffers again, but for the slack that copy_match announces
+    std::vector<uint8_t> ob(n + COPY_SLACK, 0xEE);
+    const int rcb = lanes_model(in.data(), (uint32_t)c.size(), ob.data(), (uint32_t)n);
+    if ((rcb == scginf::INFLATE_OK) != ok || (ok && !std::equal(out.begin(), out.end(), ob.begin()))) {
+        fprintf(stderr, "FAIL the lane-parallel model disagrees: rc %d where the wavefront decoder says %d\n", rcb, rc);
+        exit(1);
+    }
+    if (ok) {
+        std::vector<uint16_t> os(n + COPY_SLACK / 2, 0xEEEE);
+        const int rcs = lanes_model(in.data(), (uint32_t)c.size(), os.data(), (uint32_t)n);
+        bool same = rcs == scginf::INFLATE_OK;
+        for (size_t i = 0; same && i < n; ++i) same = os[i] == out[i];             // (a marker is >= 0x8000: no byte)
+        if (!same) {
+            fprintf(stderr, "FAIL the lane-parallel model in symbols: rc %d, or symbols that are not the text\n", rcs);
+            exit(1);
+        }
     }
     return rc;
 }

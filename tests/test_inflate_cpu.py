@@ -1,4 +1,5 @@
-"""The per-lane DEFLATE decoder of the device inflate kernel (csrc/scg_inflate.h) compiled for the host and run against
+"""The DEFLATE code of the device inflate kernels (csrc/scg_inflate.h: the per-wavefront decoder, and a model of the
+lane-parallel decoder built from the functions the two share) compiled for the host and run against
 zlib: valid streams of every block type and code shape decode identically; corrupted streams are rejected whenever zlib
 rejects them, and give zlib's output when they stay valid; AddressSanitizer watches every access (the same code runs one
 member per GPU lane, where an out-of-bounds access is a node-level fault).  No device needed."""
