@@ -9,7 +9,9 @@
 // Replaces byteme::GzipFileReader (inst/include/byteme/GzipFileReader.hpp:39-51) for the files it accepts; anything
 // unusual -- many small members, a header CRC, a stored block at a chunk start, a ratio beyond the symbol buffers, a chunk
 // that does not end where the next begins, a CRC-32 or length mismatch -- makes open_on_device() return null, and the
-// file goes to the host decoders, whose last resort is zlib itself.
+// file goes to the host decoders, whose last resort is zlib itself.  The next of them, scg_pgzip.h's, judges a stream by
+// the same rules (scg_inflate.h) and a member header by the same parser (scg_gzip.h): what is declined here is declined
+// for what it is, not for how this file reads it.
 #include <hip/hip_runtime_api.h>
 #include <zlib.h>
 
@@ -23,32 +25,18 @@
 #include <thread>
 #include <vector>
 
-#include <fcntl.h>
 #include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
-#include "scg_host.h"
-#include "scg_ingest.h"
+#include "scg_gzip.h"
 #include "scg_inflate.h"
+#include "scg_internal.hpp"
 #include "scg_textscan.h"
 
 namespace scg {
 namespace {
 
-// x^(8 len) modulo the CRC polynomial, for scginf::gf2_mult's combining of piece CRCs (scg_inflate.h): zlib's
-// crc32_combine in its 1.2.11 form squares a 32 x 32 matrix per call; thousands of pieces of one length need the power
-// only once.
 using scginf::gf2_mult;
-uint32_t x_pow_bytes(uint64_t len) {                   // x^(8 len)
-    uint32_t sq = 0x40000000u, x = 0x80000000u;         // x^1, x^0
-    for (int k = 0; k < 3; ++k) sq = gf2_mult(sq, sq);
-    for (; len; len >>= 1) {
-        if (len & 1u) x = gf2_mult(sq, x);
-        sq = gf2_mult(sq, sq);
-    }
-    return x;
-}
+using scginf::x_pow_bytes;      // (the CRC of a text from the CRCs of its pieces: scg_inflate.h)
 
 struct Declined {};                                     // (thrown inside decode(); never leaves this file)
 #define DGZ_CHECK(expr) do { if ((expr) != hipSuccess) throw Declined(); } while (0)
@@ -68,28 +56,6 @@ struct PinnedMem {
     ~PinnedMem() { if (p) (void)hipHostFree(p); }
     void alloc(size_t n) { DGZ_CHECK(hipHostMalloc(&p, n, hipHostMallocDefault)); }
 };
-struct Mapping {
-    int fd = -1;
-    const uint8_t* data = nullptr;
-    size_t size = 0;
-    explicit Mapping(const char* path) {
-        fd = ::open(path, O_RDONLY);
-        if (fd < 0) return;
-        struct stat st;
-        if (::fstat(fd, &st) != 0 || st.st_size <= 0) return;
-        void* m = ::mmap(nullptr, static_cast<size_t>(st.st_size), PROT_READ, MAP_PRIVATE, fd, 0);
-        if (m == MAP_FAILED) return;
-        data = static_cast<const uint8_t*>(m);
-        size = static_cast<size_t>(st.st_size);
-    }
-    ~Mapping() {
-        if (data) ::munmap(const_cast<uint8_t*>(data), size);
-        if (fd >= 0) ::close(fd);
-    }
-};
-
-bool trace_on() { const char* e = std::getenv("SCG_TRACE"); return e && *e && *e != '0'; }
-
 // The decoder's scratch -- the compressed file and the chunks' symbols in HBM (33 bytes per compressed byte), two pinned
 // buffers for the way there -- is kept for the next file: allocating and freeing 13 GB per call cost 20 ms of the 100 a
 // 0.4 GB file takes.  One set per process; a second call at the same time allocates its own.  scg_release_buffers() frees.
@@ -172,7 +138,7 @@ struct ScratchLease {
 // counted in part already, and is redone by the host decoders like any other input that turns out unusual late.
 class DeviceGunzipSource : public TextSource {
     int dev;
-    Mapping f;
+    MappedFile f;                                // (QUIET: a file that cannot be opened is the later rungs' to report)
     uint64_t member_start = 0, first_byte = 0, stream_end = 0;
     uint32_t tail_group = 32;                    // chunks per group of the tails' scan (scg_inflate.hip, "The tails")
     uint64_t min_member_chunks = 32;             // a member that is not the file's last is decoded here when it has this many chunks
@@ -191,7 +157,7 @@ class DeviceGunzipSource : public TextSource {
     std::vector<char> tail;        // host copy of a window's last stretch (where the cut is looked for)
 
 public:
-    DeviceGunzipSource(const char* path, int device, int threads) : dev(device), f(path), host_threads(threads), tr(trace_on()) {}
+    DeviceGunzipSource(const char* path, int device, int threads) : dev(device), f(path, MappedFile::QUIET), host_threads(threads), tr(scgapi::Trace().on) {}
     const char* kind() const override { return "gzip-device"; }
     uint64_t size_hint() const override { return (text_bytes - pos) + (ended ? 0 : (stream_end - std::min<uint64_t>(stream_end, first_byte + next_chunk * chunk_bytes)) * 8); }
     bool device_resident() const override { return true; }
@@ -215,21 +181,13 @@ public:
         return next_group();
     }
 
-    // A member's header at byte `at` of the file (RFC 1952: deflate, no header CRC; name / comment / extra fields are
-    // skipped): the chunk grid, the chain and the checksums start afresh behind it.  False: not a header this decoder takes.
+    // A member's header at byte `at0` of the file (deflate, no header CRC, no reserved flags; name / comment / extra fields
+    // are skipped), with room behind it for two bytes of stream and the trailer: the chunk grid, the chain and the checksums
+    // start afresh behind it.  False: not a header this decoder takes.
     bool member_at(uint64_t at0) {
-        const uint8_t* p = f.data + at0;
-        if (at0 + 18 + 2 > f.size) return false;
-        if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || (p[3] & 0xE2)) return false;
-        uint64_t at = at0 + 10;
-        if (p[3] & 4) { if (at + 2 > f.size) return false; at += 2 + (f.data[at] | (static_cast<uint64_t>(f.data[at + 1]) << 8)); }
-        for (int field = 0; field < 2; ++field) {
-            if (p[3] & (field == 0 ? 8 : 16)) {
-                while (at < f.size && f.data[at]) ++at;
-                ++at;
-            }
-        }
-        if (at + 8 + 2 > f.size) return false;
+        gz::MemberHeader h;
+        if (!gz::parse_member_header(f.bytes(), f.size, at0, h) || (h.flags & 0xE2) || f.size - h.payload < 10) return false;
+        const uint64_t at = h.payload;
         member_start = at0;
         first_byte = at;
         stream_end = f.size - 8;                  // (where the LAST member's stream ends; an earlier member's end is found by decoding)
@@ -441,10 +399,8 @@ private:
             }
             text_total += made;
             if (final_seen) {
-                const uint8_t* t = f.data + trailer;
-                const uint32_t want_crc = t[0] | (uint32_t(t[1]) << 8) | (uint32_t(t[2]) << 16) | (uint32_t(t[3]) << 24);
-                const uint32_t want_size = t[4] | (uint32_t(t[5]) << 8) | (uint32_t(t[6]) << 16) | (uint32_t(t[7]) << 24);
-                if (static_cast<uint32_t>(crc_acc) != want_crc || static_cast<uint32_t>(text_total) != want_size) return false;
+                const gz::Trailer want = gz::read_trailer(f.bytes() + trailer);
+                if (static_cast<uint32_t>(crc_acc) != want.crc || static_cast<uint32_t>(text_total) != want.isize) return false;
             }
             // (every copy out of the old text was enqueued before this point and the device has been synchronised since)
             DGZ_CHECK(hipDeviceSynchronize());

@@ -12,6 +12,7 @@
 //   - "line numbers" in messages advance by exactly four per record, as the reference counts them.
 // Unlike the reference's byte-at-a-time virtual-call loop this scanner works on large buffers
 // with memchr, and only the sequence bytes are kept (names and qualities never leave this file).
+#include "scg_gzip.h"
 #include "scg_host.h"
 #include "scg_ingest.h"
 
@@ -56,8 +57,7 @@ struct FastqStream::Impl {
             got = std::fread(header, 1, 3, f);
             std::fclose(f);
         }
-        // byteme/magic_numbers.hpp:19-22
-        gz = (got >= 2 && header[0] == 0x1f && header[1] == 0x8b);
+        gz = got >= 2 && scg::gz::is_gzip(header);      // as the reference picks its reader
         if (gz) {
             gzf = gzopen(p, "rb");
             if (!gzf) throw Error(SCG_ERR_IO, "failed to open file at '" + path + "'");
@@ -275,7 +275,7 @@ bool ParallelFastq::is_plain_file(const char* path) {
     if (!f) return false;
     size_t got = std::fread(h, 1, 2, f);
     std::fclose(f);
-    return !(got == 2 && h[0] == 0x1f && h[1] == 0x8b);
+    return !(got == 2 && gz::is_gzip(h));
 }
 
 ParallelFastq::ParallelFastq(const char* path, int nthreads) : impl(new Impl) {

@@ -7,9 +7,15 @@
 // every wavefront of scg_inflate.hip's kernels inflates one member (or one chunk of an ordinary gzip stream), its
 // Huffman tables in LDS; the text never exists on the host.
 //
-// Two decoders share what is a rule of the format -- the bit reader, block headers and their tables (fixed_tables,
-// read_dynamic_tables), the length and distance symbols (length_* / dist_*, read_match, decode_here), a match's copy
-// (copy_match):
+// This is the project's ONE statement of the format's rules.  The host's chunk decoder (scg_pgzip.h), which takes the files
+// the device's decoder hands back, has tables and a loop of its own, tuned for a host core, but takes every rule from
+// here: a block header's limits, code-length code and repeat codes (read_code_lengths, for any bit reader), when a set of
+// code lengths is a code (code_set_allowed), the fixed code (fixed_code_lengths), the bases and extra bits of length and
+// distance symbols (length_* / dist_*), the markers.  (One exception, by measurement: the dynamic block filter, below.)
+// The gzip container around the stream is scg_gzip.h's.
+//
+// The two device decoders share more -- the bit reader, the tables (fixed_tables, read_dynamic_tables), read_match and
+// decode_here, a match's copy (copy_match):
 //   * the lane-parallel decoder (scg_inflate.hip: inflate_lanes; the product's default, and stage 1 of the gzip path)
 //     decodes 128 bit offsets at a time with decode_here and keeps only its scheduling -- batches, the chain walk,
 //     deferred matches -- in the device file;
@@ -18,8 +24,9 @@
 //     the lanes only differ where bytes move (a match is copied 64 bytes at a time, one per lane).
 // Everything is plain C++, so the tests compile the very same code for the host (tests/inflate_harness.cpp:
 // differential runs against zlib, corrupted streams under ASan): inflate_member with "wavefronts" of 1, 7 and 64
-// lanes, and a model of the lane-parallel decoder's arithmetic built from the same functions.  The CRC code's GF(2)
-// multiply (gf2_mult, at the end) lives here too, for the device's CRC kernel and the host side of the gzip path.
+// lanes, a model of the lane-parallel decoder's arithmetic built from the same functions, and the host's chunk decoder
+// beside them.  The CRC code's GF(2) arithmetic (gf2_mult, x_pow_bytes, at the end) lives here too, for the device's CRC
+// kernel and the host side of the gzip path.
 //
 // Accept / reject behaviour follows zlib's inflate (inflate.c, inftrees.c) rule by rule -- over-subscribed and
 // incomplete code sets, missing end-of-block code, too many length / distance symbols, invalid stored block lengths,
@@ -32,7 +39,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__)
-#define SCG_HD __host__ __device__ __forceinline__
+#define SCG_HD __host__ __device__ inline __attribute__((always_inline))      // (__forceinline__, without the HIP runtime's header)
 #else
 #define SCG_HD inline
 #endif
@@ -48,6 +55,7 @@ enum : int {
 constexpr int LIT_BITS = 9, DIST_BITS = 7;                   // primary tables of the literal/length and the distance code: inflate_member
 constexpr int LANES_LIT_BITS = 10, LANES_DIST_BITS = 8;      // the lane-parallel decoder (11 / 9 bits: no gain -- long codes are rare in FASTQ)
 constexpr int CL_BITS = 7;                                   // the code-length code's longest code
+constexpr int LENS_BYTES = 320 + 19;                         // a block header's code lengths, the code-length code's own behind them
 constexpr uint32_t IN_SLACK = 64; // bytes readable beyond a member's payload (the caller pads its buffer)
 
 // One block's tables (LDS on the device, one set per wavefront).
@@ -211,9 +219,22 @@ SCG_HD uint32_t reverse_bits(uint32_t code, int len) {
     return r;
 }
 
+// Whether zlib takes a set of code lengths (inftrees.c: inflate_table), count[l] codes of length l = 1 .. 15, the longest
+// of `max` >= 1 bits: never an over-subscribed set; an incomplete one only as a literal/length or distance code (kind 1)
+// whose only code has one bit, and never as the code-length code (kind 0).
+SCG_HD bool code_set_allowed(const uint16_t* count, int max, int kind) {
+    int left = 1;
+    for (int l = 1; l <= 15; ++l) {
+        left <<= 1;
+        left -= count[l];
+        if (left < 0) return false;                           // over-subscribed
+    }
+    if (left > 0 && (kind == 0 || max != 1)) return false;    // incomplete
+    return true;
+}
+
 // Builds the decoding tables of one canonical Huffman code from lens[0 .. n) (inftrees.c: inflate_table).
-// kind: 0 = code-length code (incomplete sets rejected), 1 = literal/length or distance code (an incomplete set is
-// accepted only when its longest code has one bit).  Returns false for a set zlib rejects.
+// kind: 0 = code-length code, 1 = literal/length or distance code (code_set_allowed).  Returns false for a set zlib rejects.
 // `table` has 1 << tbits entries; `count`, `sym`, `offs` as in LaneTables.  lens may lie inside `table`: it is not read
 // any more once the table is being written.
 SCG_HD bool build_code(const uint8_t* lens, int n, int kind, uint16_t* table, int tbits, uint16_t* count, uint16_t* sym, uint16_t* offs) {
@@ -221,15 +242,7 @@ SCG_HD bool build_code(const uint8_t* lens, int n, int kind, uint16_t* table, in
     for (int s = 0; s < n; ++s) count[lens[s]] = static_cast<uint16_t>(count[lens[s]] + 1);
     int max = 15;
     while (max >= 1 && count[max] == 0) --max;
-    if (max >= 1) {
-        int left = 1;
-        for (int l = 1; l <= 15; ++l) {
-            left <<= 1;
-            left -= count[l];
-            if (left < 0) return false;                       // over-subscribed
-        }
-        if (left > 0 && (kind == 0 || max != 1)) return false;   // incomplete set
-    }
+    if (max >= 1 && !code_set_allowed(count, max, kind)) return false;
     // (max == 0: no codes at all -- every lookup below fails, which is the error zlib raises when such a code is used)
     offs[1] = 0;
     for (int l = 1; l < 15; ++l) offs[l + 1] = static_cast<uint16_t>(offs[l] + count[l]);
@@ -255,7 +268,10 @@ SCG_HD bool build_code(const uint8_t* lens, int n, int kind, uint16_t* table, in
 
 // A code that the primary table does not resolve: canonical decoding one bit at a time.  Returns the symbol, or -1
 // for a bit pattern that is no code.  Needs 15 bits in the reader.
-SCG_HD int decode_slow(BitReader& br, const uint16_t* count, const uint16_t* sym) {
+// A Reader (BitReader here, pgz::Bits on the host) has bits(n), refill(), overrun() and the fields buf (LSB first) and cnt;
+// how far it may look beyond its input, and what overrun() therefore means, is its own buffer contract.
+template<class Reader>
+SCG_HD int decode_slow(Reader& br, const uint16_t* count, const uint16_t* sym) {
     uint32_t code = 0, first = 0, index = 0;
     uint32_t b = static_cast<uint32_t>(br.buf);
     for (int l = 1; l <= 15; ++l) {
@@ -274,7 +290,8 @@ SCG_HD int decode_slow(BitReader& br, const uint16_t* count, const uint16_t* sym
     return -1;
 }
 
-SCG_HD int decode_symbol(BitReader& br, const uint16_t* table, int tbits, const uint16_t* count, const uint16_t* sym) {
+template<class Reader>
+SCG_HD int decode_symbol(Reader& br, const uint16_t* table, int tbits, const uint16_t* count, const uint16_t* sym) {
     const uint32_t e = table[static_cast<uint32_t>(br.buf) & ((1u << tbits) - 1u)];
     if (e) {
         const uint32_t l = e >> 12;
@@ -353,23 +370,29 @@ SCG_HD bool build_tables(TablesT& T, const uint8_t* lens, int nlen, int ndist) {
     return true;
 }
 
-// The tables of the fixed code (inflate.c: fixedtables).
-template<class TablesT>
-SCG_HD bool fixed_tables(TablesT& T, uint8_t* lens) {
+// The lengths of the fixed code (inflate.c: fixedtables): 288 literal/length codes, then 32 distance codes.
+SCG_HD void fixed_code_lengths(uint8_t* lens) {
     for (int s = 0; s < 144; ++s) lens[s] = 8;
     for (int s = 144; s < 256; ++s) lens[s] = 9;
     for (int s = 256; s < 280; ++s) lens[s] = 7;
     for (int s = 280; s < 288; ++s) lens[s] = 8;
     for (int s = 0; s < 32; ++s) lens[288 + s] = 5;
+}
+template<class TablesT>
+SCG_HD bool fixed_tables(TablesT& T, uint8_t* lens) {
+    fixed_code_lengths(lens);
     return build_tables(T, lens, 288, 32);
 }
 
-// The code lengths of a dynamic-Huffman block header (br stands behind BFINAL and BTYPE) and the block's two tables.
-// False for anything zlib would reject (too many codes, an over-subscribed or incomplete set, no end-of-block code).
-template<class TablesT>
-SCG_HD bool read_dynamic_tables(BitReader& br, TablesT& T, uint8_t* lens) {
-        const int nlen = static_cast<int>(br.bits(5)) + 257;
-    const int ndist = static_cast<int>(br.bits(5)) + 1;
+// The code lengths of a dynamic-Huffman block header (br stands behind BFINAL and BTYPE, 14 bits in its buffer): nlen
+// literal/length and ndist distance lengths to lens[0 ...), which has room for LENS_BYTES.  False for anything zlib would
+// reject up to there (too many codes, an over-subscribed or incomplete code-length code, a repeat with nothing to repeat or
+// beyond the end, no end-of-block code).  The code-length code lives in the caller's cltab (1 << CL_BITS entries), count
+// (16), sym (19) and offs (16) while this runs.
+template<class Reader>
+SCG_HD bool read_code_lengths(Reader& br, uint8_t* lens, int& nlen, int& ndist, uint16_t* cltab, uint16_t* count, uint16_t* sym, uint16_t* offs) {
+    nlen = static_cast<int>(br.bits(5)) + 257;
+    ndist = static_cast<int>(br.bits(5)) + 1;
     const int ncode = static_cast<int>(br.bits(4)) + 4;
     if (nlen > 286 || ndist > 30) return false;                          // "too many length or distance symbols"
     // the code-length code: its 19 lengths sit behind the 320 bytes reserved for the lengths proper
@@ -382,13 +405,12 @@ SCG_HD bool read_dynamic_tables(BitReader& br, TablesT& T, uint8_t* lens) {
         const uint32_t at = static_cast<uint32_t>((i < 12 ? order_lo >> (5 * i) : order_hi >> (5 * (i - 12))) & 31u);
         cl[at] = static_cast<uint8_t>(br.bits(3));
     }
-    // (its symbols and counts borrow the distance code's arrays, which are built afterwards)
-    if (!build_code(cl, 19, 0, T.dtab, CL_BITS, T.dcount, T.dsym, T.offs)) return false;     // "invalid code lengths set"
+    if (!build_code(cl, 19, 0, cltab, CL_BITS, count, sym, offs)) return false;              // "invalid code lengths set"
     int have = 0;
     while (have < nlen + ndist) {
         if (br.overrun()) return false;
         br.refill();
-        const int s = decode_symbol(br, T.dtab, CL_BITS, T.dcount, T.dsym);
+        const int s = decode_symbol(br, cltab, CL_BITS, count, sym);
         if (s < 0) return false;
         if (s < 16) { lens[have++] = static_cast<uint8_t>(s); continue; }
         uint8_t fill = 0;
@@ -405,9 +427,23 @@ SCG_HD bool read_dynamic_tables(BitReader& br, TablesT& T, uint8_t* lens) {
         if (have + rep > nlen + ndist) return false;                     // "invalid bit length repeat"
         while (rep--) lens[have++] = fill;
     }
-    if (lens[256] == 0) return false;                                    // "invalid code -- missing end-of-block"
+    return lens[256] != 0;                                               // "invalid code -- missing end-of-block"
+}
+
+// A dynamic-Huffman block header and the block's two tables; false for anything zlib would reject.
+// (the code-length code borrows the distance code's arrays, which are built afterwards)
+template<class TablesT>
+SCG_HD bool read_dynamic_tables(BitReader& br, TablesT& T, uint8_t* lens) {
+    int nlen, ndist;
+    if (!read_code_lengths(br, lens, nlen, ndist, T.dtab, T.dcount, T.dsym, T.offs)) return false;
     return build_tables(T, lens, nlen, ndist);
 }
+
+// The dynamic block filter -- the cheap test that proposes block starts to the chunked gzip decoders (BFINAL = 0, BTYPE = 2,
+// HLIT and HDIST <= 29, Kraft sum of the code-length code = 128) -- is the ONE rule that stays spelled twice: branch-free
+// in gunzip_find_kernel (scg_inflate.hip), with early exits in pgz::find_dynamic_block (scg_pgzip.h).  As one branch-free
+// function here it was tried and measured slower on both sides (profiles/gzip_rules_ab.txt).  It only proposes: what passes
+// is parsed in full by read_code_lengths, so a drift between the two moves where chunks start, never what is accepted.
 
 // The decoder writes bytes (BGZF members: the text itself) or 16-bit symbols (chunks of an ordinary gzip stream, decoded
 // without the 32 KiB of text in front of them: a symbol is a byte, or MARKER + k for "byte k of the window I do not have";
@@ -540,6 +576,19 @@ SCG_HD uint32_t gf2_mult(uint32_t a, uint32_t b) {
         b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
     }
     return p;
+}
+// x^(8 len): the factor that moves a CRC across len bytes.  By squaring (x^1, x^2, x^4 ...: the series the device's table
+// of powers holds, scg_inflate.hip: crc_powers) -- zlib's crc32_combine in its 1.2.11 form squares a 32 x 32 matrix per
+// call; thousands of pieces of one length need the power only once.
+constexpr uint32_t GF2_X0 = 0x80000000u, GF2_X1 = 0x40000000u;
+SCG_HD uint32_t x_pow_bytes(uint64_t len) {
+    uint32_t sq = GF2_X1, x = GF2_X0;
+    for (int k = 0; k < 3; ++k) sq = gf2_mult(sq, sq);          // x^8
+    for (; len; len >>= 1) {
+        if (len & 1u) x = gf2_mult(sq, x);
+        sq = gf2_mult(sq, sq);
+    }
+    return x;
 }
 
 }  // namespace scginf

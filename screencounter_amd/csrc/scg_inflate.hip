@@ -798,7 +798,7 @@ size_t inflate_input_slack() { return scginf::IN_SLACK; }
 const CrcPowers& crc_powers() {
     static const CrcPowers P = [] {
         CrcPowers t;
-        uint32_t p = 1u << 30;                 // x^1
+        uint32_t p = scginf::GF2_X1;           // x^(2^k), by the squaring of scginf::x_pow_bytes
         t.x2n[0] = p;
         for (int k = 1; k < 32; ++k) t.x2n[k] = p = scginf::gf2_mult(p, p);
         return t;

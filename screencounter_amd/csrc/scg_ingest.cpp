@@ -2,13 +2,13 @@
 #include "scg_ingest.h"
 #include "scg_host.h"
 #include "scg_pgzip.hpp"
+#include "scg_gzip.h"
 
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
-#include <dlfcn.h>
 #include <exception>
 #include <fcntl.h>
 #include <mutex>
@@ -121,6 +121,38 @@ size_t strict_record_end(const char* data, size_t size, size_t p, const char** s
     return l4 ? static_cast<size_t>(l4 + 1 - data) : size;
 }
 
+MappedFile::MappedFile(const char* path, unsigned options) {
+    auto give_up = [&](const std::string& why) {
+        if (fd >= 0) { ::close(fd); fd = -1; }
+        size = mapped = 0;
+        if (!(options & QUIET)) throw Error(SCG_ERR_IO, why);
+    };
+    fd = ::open(path, O_RDONLY);
+    if (fd < 0) { give_up(std::string("failed to open file at '") + path + "'"); return; }
+    struct stat st;
+    if (::fstat(fd, &st) != 0) { give_up("failed to stat the FASTQ file"); return; }
+    size = static_cast<size_t>(st.st_size);
+    void* m = nullptr;
+    if (options & ZERO_PAGE) {
+        mapped = ((size + 4095) & ~size_t(4095)) + 4096;
+        m = ::mmap(nullptr, mapped, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+        if (m != MAP_FAILED && size && ::mmap(m, size, PROT_READ, MAP_PRIVATE | MAP_FIXED, fd, 0) == MAP_FAILED) {
+            ::munmap(m, mapped);
+            m = MAP_FAILED;
+        }
+    } else if (size) {
+        mapped = size;
+        m = ::mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (m != MAP_FAILED && !options) ::madvise(m, size, MADV_SEQUENTIAL);
+    }
+    if (m == MAP_FAILED) { give_up("failed to map the FASTQ file"); return; }
+    data = static_cast<const char*>(m);
+}
+MappedFile::~MappedFile() {
+    if (data && mapped) ::munmap(const_cast<char*>(data), mapped);
+    if (fd >= 0) ::close(fd);
+}
+
 namespace {
 
 // The largest c <= len such that two consecutive ordinary records end exactly at c, searched among the line starts of
@@ -150,36 +182,6 @@ size_t find_cut(const char* data, size_t len, size_t slack) {
 }
 
 namespace {
-
-struct MappedFile {
-    int fd = -1;
-    const char* data = nullptr;
-    size_t size = 0;          // bytes of content
-    size_t mapped = 0;        // bytes of the mapping (>= size for an adopted anonymous one)
-    explicit MappedFile(const char* path) {
-        fd = ::open(path, O_RDONLY);
-        if (fd < 0) throw Error(SCG_ERR_IO, std::string("failed to open file at '") + path + "'");
-        struct stat st;
-        if (::fstat(fd, &st) != 0) { ::close(fd); throw Error(SCG_ERR_IO, "failed to stat the FASTQ file"); }
-        size = static_cast<size_t>(st.st_size);
-        if (size) {
-            void* m = ::mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m == MAP_FAILED) { ::close(fd); throw Error(SCG_ERR_IO, "failed to map the FASTQ file"); }
-            ::madvise(m, size, MADV_SEQUENTIAL);
-            data = static_cast<const char*>(m);
-            mapped = size;
-        }
-    }
-    // Adopts an anonymous mapping of `reserved` bytes holding `content` bytes of text.
-    MappedFile(char* anonymous, size_t reserved, size_t content) : data(anonymous), size(content), mapped(reserved) {}
-    MappedFile(MappedFile&& o) noexcept : fd(o.fd), data(o.data), size(o.size), mapped(o.mapped) { o.fd = -1; o.data = nullptr; o.size = o.mapped = 0; }
-    ~MappedFile() {
-        if (data && mapped) ::munmap(const_cast<char*>(data), mapped);
-        if (fd >= 0) ::close(fd);
-    }
-    MappedFile(const MappedFile&) = delete;
-    MappedFile& operator=(const MappedFile&) = delete;
-};
 
 // ---- plain file: windows are copied out of a mapping of the file by several threads.  Copying from the mapping
 //      runs at 85-95 GB/s on tmpfs with 16 threads (pread() into the same pinned buffers: 50-58 GB/s, below the PCIe
@@ -345,71 +347,41 @@ public:
 //      each straight into its place in the window ----
 struct BgzfMember {
     size_t off, csize;
-    uint32_t isize;
+    size_t payload;               // where its DEFLATE stream begins, from `off`
+    uint8_t flags;
+    gz::Trailer trailer;
 };
 
 // Parses the member header at data[off]; false if it is not a BGZF member.
-bool bgzf_member(const char* data, size_t size, size_t off, BgzfMember& m) {
-    const unsigned char* p = reinterpret_cast<const unsigned char*>(data) + off;
-    if (size - off < 28) return false;
-    if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return false;
-    const size_t xlen = p[10] | (static_cast<size_t>(p[11]) << 8);
-    if (size - off < 12 + xlen + 8) return false;
-    size_t x = 12;
-    size_t bsize = 0;
-    while (x + 4 <= 12 + xlen) {
-        const size_t slen = p[x + 2] | (static_cast<size_t>(p[x + 3]) << 8);
-        if (p[x] == 'B' && p[x + 1] == 'C' && slen == 2 && x + 6 <= 12 + xlen) {
-            bsize = (p[x + 4] | (static_cast<size_t>(p[x + 5]) << 8)) + 1;
-            break;
-        }
-        x += 4 + slen;
-    }
-    if (!bsize || bsize < 12 + xlen + 8 || off + bsize > size) return false;
-    const unsigned char* t = p + bsize - 4;
+bool bgzf_member(const MappedFile& f, size_t off, BgzfMember& m) {
+    gz::MemberHeader h;
+    if (f.size - off < 28 || !gz::parse_member_header(f.bytes(), f.size, off, h, gz::FEXTRA) || !(h.flags & gz::FEXTRA)) return false;
+    const size_t bsize = gz::bgzf_block_size(f.bytes(), h);
+    if (!bsize || bsize < 12 + h.extra_len + 8 || off + bsize > f.size) return false;
     m.off = off;
     m.csize = bsize;
-    m.isize = t[0] | (static_cast<uint32_t>(t[1]) << 8) | (static_cast<uint32_t>(t[2]) << 16) | (static_cast<uint32_t>(t[3]) << 24);
+    m.payload = h.payload - off;
+    m.flags = h.flags;
+    m.trailer = gz::read_trailer(f.bytes() + off + bsize - 8);
     return true;
 }
 
-// libdeflate (whole-buffer DEFLATE, 2-3 x zlib's inflate) is part of this image as a shared library without headers;
-// it is looked up at run time and used for the members it accepts (CRC and size checked by it, all input consumed);
+// libdeflate (gz::libdeflate) is used for the members it accepts (CRC and size checked by it, all input consumed);
 // anything else -- and everything when it is absent or SCG_LIBDEFLATE=0 -- is zlib's, whose verdict and message count.
-struct Libdeflate {
-    void* (*alloc)() = nullptr;
-    void (*release)(void*) = nullptr;
-    int (*gzip_ex)(void*, const void*, size_t, void*, size_t, size_t*, size_t*) = nullptr;
-    Libdeflate() {
-        void* h = ::dlopen("libdeflate.so.0", RTLD_NOW | RTLD_LOCAL);
-        if (!h) return;
-        alloc = reinterpret_cast<void* (*)()>(::dlsym(h, "libdeflate_alloc_decompressor"));
-        release = reinterpret_cast<void (*)(void*)>(::dlsym(h, "libdeflate_free_decompressor"));
-        gzip_ex = reinterpret_cast<int (*)(void*, const void*, size_t, void*, size_t, size_t*, size_t*)>(::dlsym(h, "libdeflate_gzip_decompress_ex"));
-        if (!alloc || !release || !gzip_ex) alloc = nullptr;
-    }
-    bool usable() const {
-        const char* e = std::getenv("SCG_LIBDEFLATE");
-        return alloc != nullptr && !(e && *e == '0');
-    }
-};
-const Libdeflate& libdeflate() {
-    static const Libdeflate* L = new Libdeflate;      // (never unloaded)
-    return *L;
-}
 struct ThreadDecompressor {
     void* d = nullptr;
-    ~ThreadDecompressor() { if (d) libdeflate().release(d); }
+    void (*release)(void*) = nullptr;
+    ~ThreadDecompressor() { if (d) release(d); }
 };
 
 void inflate_member(const char* src, size_t csize, char* dst, uint32_t isize) {
-    const Libdeflate& L = libdeflate();
-    if (L.usable()) {
+    const gz::Libdeflate* L = gz::libdeflate();
+    if (L && L->alloc) {
         thread_local ThreadDecompressor td;
-        if (!td.d) td.d = L.alloc();
+        if (!td.d) { td.d = L->alloc(); td.release = L->release; }
         if (td.d) {
             size_t used = 0, made = 0;
-            if (L.gzip_ex(td.d, src, csize, dst, isize, &used, &made) == 0 && used == csize && made == isize) return;
+            if (L->gzip_ex(td.d, src, csize, dst, isize, &used, &made) == 0 && used == csize && made == isize) return;
         }
     }
     z_stream zs;
@@ -437,7 +409,7 @@ public:
     static bool looks_like(const char* path) {
         MappedFile g(path);
         BgzfMember m;
-        return g.size && bgzf_member(g.data, g.size, 0, m);
+        return g.size && bgzf_member(g, 0, m);
     }
     bool has_members() const override { return true; }
     size_t next_members(char* staging, size_t cap, size_t slack, size_t cap_text, std::vector<CompressedMember>& members, size_t& text_bytes,
@@ -465,24 +437,21 @@ public:
         const size_t window_start = off;
         while (off < f.size) {
             BgzfMember m;
-            if (!bgzf_member(f.data, f.size, off, m)) { odd = true; return 0; }
-            const unsigned char* p = reinterpret_cast<const unsigned char*>(f.data) + off;
-            const size_t xlen = p[10] | (static_cast<size_t>(p[11]) << 8);
+            if (!bgzf_member(f, off, m)) { odd = true; return 0; }
             // FEXTRA only (what bgzip writes): names, comments and header CRCs are for zlib to judge
-            if (p[3] != 4 || m.csize < 12 + xlen + 8) { odd = true; return 0; }
-            const size_t payload = m.csize - 12 - xlen - 8;
-            if (in + payload + slack > cap || out + m.isize > cap_text) break;
-            const unsigned char* t = p + m.csize - 8;
+            if (m.flags != gz::FEXTRA) { odd = true; return 0; }
+            const size_t payload = m.csize - m.payload - 8;
+            if (in + payload + slack > cap || out + m.trailer.isize > cap_text) break;
             CompressedMember c;
             c.in_off = static_cast<uint32_t>(in);
             c.in_len = static_cast<uint32_t>(payload);
             c.out_off = static_cast<uint32_t>(out);
-            c.out_len = m.isize;
-            c.crc = t[0] | (static_cast<uint32_t>(t[1]) << 8) | (static_cast<uint32_t>(t[2]) << 16) | (static_cast<uint32_t>(t[3]) << 24);
+            c.out_len = m.trailer.isize;
+            c.crc = m.trailer.crc;
             members.push_back(c);
-            from.push_back(off + 12 + xlen);
+            from.push_back(off + m.payload);
             in += payload;
-            out += m.isize;
+            out += m.trailer.isize;
             off += m.csize;
         }
         if (members.empty()) { odd = true; return 0; }            // one member larger than a window
@@ -514,22 +483,22 @@ protected:
         size_t at = have;
         while (off < f.size) {
             BgzfMember m;
-            if (!bgzf_member(f.data, f.size, off, m)) {
+            if (!bgzf_member(f, off, m)) {
                 // a member without the size subfield in the middle of the file: not a format this source understands
                 odd = true;
                 return have;
             }
-            if (at + m.isize > cap) break;
+            if (at + m.trailer.isize > cap) break;
             batch.push_back(m);
             where.push_back(at);
-            at += m.isize;
+            at += m.trailer.isize;
             off += m.csize;
         }
         if (off >= f.size) exhausted = true;
         if (batch.empty() && !exhausted) { odd = true; return have; }     // one member larger than a window
         try {
             pool.run(static_cast<int>(batch.size()), [&](int i) {
-                if (batch[i].isize) inflate_member(f.data + batch[i].off, batch[i].csize, dst + where[i], batch[i].isize);
+                if (batch[i].trailer.isize) inflate_member(f.data + batch[i].off, batch[i].csize, dst + where[i], batch[i].trailer.isize);
             });
         } catch (const Error&) {
             // a corrupt member: the sequential reader reports it the way the reference does -- zlib's message with the
@@ -579,8 +548,8 @@ protected:
 //      ($SCG_GZIP_WHOLE_GB, default 8, 0 = never) bounds the memory this takes; larger files, files libdeflate
 //      declines, and files with anything but whole gzip members in them are streamed through zlib as before ----
 std::unique_ptr<MappedFile> inflate_whole(const char* path) {
-    const Libdeflate& L = libdeflate();
-    if (!L.usable()) return nullptr;
+    const gz::Libdeflate* L = gz::libdeflate();
+    if (!L || !L->alloc) return nullptr;
     size_t limit = size_t(8) << 30;
     if (const char* e = std::getenv("SCG_GZIP_WHOLE_GB")) limit = static_cast<size_t>(std::max(0.0, std::atof(e)) * double(size_t(1) << 30));
     MappedFile in(path);
@@ -590,18 +559,18 @@ std::unique_ptr<MappedFile> inflate_whole(const char* path) {
     const size_t cap = std::min(limit, in.size * 24 + (size_t(1) << 20)) + 4096;
     void* m = ::mmap(nullptr, cap, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
     if (m == MAP_FAILED) return nullptr;
-    void* d = L.alloc();
+    void* d = L->alloc();
     size_t at = 0, made = 0;
     bool ok = d != nullptr;
     while (ok && at < in.size) {
         size_t used = 0, got = 0;
-        const unsigned char* p = reinterpret_cast<const unsigned char*>(in.data) + at;
-        ok = in.size - at >= 18 && p[0] == 0x1f && p[1] == 0x8b &&
-             L.gzip_ex(d, p, in.size - at, static_cast<char*>(m) + made, cap - 4096 - made, &used, &got) == 0 && used > 0;
+        const uint8_t* p = in.bytes() + at;
+        ok = in.size - at >= 18 && gz::is_gzip(p) &&
+             L->gzip_ex(d, p, in.size - at, static_cast<char*>(m) + made, cap - 4096 - made, &used, &got) == 0 && used > 0;
         at += used;
         made += got;
     }
-    if (d) L.release(d);
+    if (d) L->release(d);
     if (!ok) {                     // (too large, corrupt, trailing bytes ...: zlib's stream decides)
         ::munmap(m, cap);
         return nullptr;
@@ -615,35 +584,11 @@ std::unique_ptr<MappedFile> inflate_whole(const char* path) {
 //      stream, a header CRC, a ratio beyond its buffers -- sets unusual(): the caller redoes the file with the
 //      streams above, whose verdict is zlib's ----
 class PgzipSource : public CarrySource {
-    int fd = -1;
-    uint8_t* map = nullptr;
-    size_t mapped = 0, csize = 0;
-    std::unique_ptr<ParallelGunzip> pg;
+    MappedFile f;                 // (the decoder's bit reader looks a few bytes beyond the last one)
+    ParallelGunzip pg;
     uint64_t produced = 0;
 public:
-    PgzipSource(const char* path, int nthreads) {
-        threads = nthreads;
-        fd = ::open(path, O_RDONLY);
-        if (fd < 0) throw Error(SCG_ERR_IO, std::string("failed to open file at '") + path + "'");
-        struct stat st;
-        if (::fstat(fd, &st) != 0) { ::close(fd); throw Error(SCG_ERR_IO, "failed to stat the FASTQ file"); }
-        csize = static_cast<size_t>(st.st_size);
-        // the file, followed by a page of zeros: the decoder's bit reader looks a few bytes beyond the last one
-        mapped = ((csize + 4095) & ~size_t(4095)) + 4096;
-        void* m = ::mmap(nullptr, mapped, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        if (m == MAP_FAILED) { ::close(fd); throw Error(SCG_ERR_IO, "failed to map the FASTQ file"); }
-        if (csize && ::mmap(m, csize, PROT_READ, MAP_PRIVATE | MAP_FIXED, fd, 0) == MAP_FAILED) {
-            ::munmap(m, mapped); ::close(fd);
-            throw Error(SCG_ERR_IO, "failed to map the FASTQ file");
-        }
-        map = static_cast<uint8_t*>(m);
-        pg.reset(new ParallelGunzip(map, csize, nthreads));
-    }
-    ~PgzipSource() override {
-        pg.reset();
-        if (map) ::munmap(map, mapped);
-        if (fd >= 0) ::close(fd);
-    }
+    PgzipSource(const char* path, int nthreads) : f(path, MappedFile::ZERO_PAGE), pg(f.bytes(), f.size, nthreads) { threads = nthreads; }
     static bool wanted(const char* path, int nthreads) {
         const char* e = std::getenv("SCG_PGZIP");             // test hook: 0 keeps the single inflate streams
         if (e && *e == '0') return false;
@@ -652,11 +597,11 @@ public:
         return ParallelGunzip::chunk_size_for(static_cast<size_t>(st.st_size), nthreads) != 0;
     }
     const char* kind() const override { return "gzip-parallel"; }
-    uint64_t size_hint() const override { return static_cast<uint64_t>(csize) * 8 > produced ? static_cast<uint64_t>(csize) * 8 - produced : 4096; }
+    uint64_t size_hint() const override { return static_cast<uint64_t>(f.size) * 8 > produced ? static_cast<uint64_t>(f.size) * 8 - produced : 4096; }
 protected:
     size_t fill(char* dst, size_t have, size_t cap) override {
-        const size_t got = pg->read(dst + have, cap - have);
-        if (pg->failed()) { odd = true; return have; }
+        const size_t got = pg.read(dst + have, cap - have);
+        if (pg.failed()) { odd = true; return have; }
         if (got < cap - have) exhausted = true;
         produced += got;
         return have + got;
@@ -672,7 +617,7 @@ bool TextSource::ordinary_gzip(const char* path, int threads) {
     if (!fp) return false;
     const size_t got = std::fread(h, 1, 2, fp);
     std::fclose(fp);
-    if (got != 2 || h[0] != 0x1f || h[1] != 0x8b) return false;
+    if (got != 2 || !gz::is_gzip(h)) return false;
     return !BgzfSource::looks_like(path) && PgzipSource::wanted(path, threads);
 }
 
@@ -686,8 +631,7 @@ std::unique_ptr<TextSource> TextSource::open(const char* path, int threads, bool
         got = std::fread(h, 1, 2, fp);
         std::fclose(fp);
     }
-    const bool gz = got == 2 && h[0] == 0x1f && h[1] == 0x8b;      // byteme/magic_numbers.hpp:19-22
-    if (!gz) return std::unique_ptr<TextSource>(new PlainSource(path, threads));
+    if (!(got == 2 && gz::is_gzip(h))) return std::unique_ptr<TextSource>(new PlainSource(path, threads));
     if (BgzfSource::looks_like(path)) return std::unique_ptr<TextSource>(new BgzfSource(path, threads));
     if (parallel_gzip && PgzipSource::wanted(path, gzip_threads)) return std::unique_ptr<TextSource>(new PgzipSource(path, gzip_threads));
     if (std::unique_ptr<MappedFile> text = inflate_whole(path)) {

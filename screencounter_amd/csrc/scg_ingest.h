@@ -45,6 +45,28 @@ void release_device_gunzip_scratch();
 // `slack` bytes); 0 if there is none.
 size_t find_cut(const char* data, size_t len, size_t slack = size_t(1) << 20);
 
+// A file mapped read-only (or an anonymous mapping that holds text, adopted).  Errors are thrown with the reference's
+// texts unless QUIET is asked for: then data stays null.  A plain mapping is advised MADV_SEQUENTIAL; the chunked gzip
+// decoders, which ask for options, read theirs at many places at once.
+struct MappedFile {
+    enum : unsigned {
+        ZERO_PAGE = 1,      // a page of zeros follows the file: for bit readers that look a few bytes beyond the last one
+        QUIET = 2,          // no exception when the file cannot be opened or mapped
+    };
+    int fd = -1;
+    const char* data = nullptr;
+    size_t size = 0;          // bytes of content
+    size_t mapped = 0;        // bytes of the mapping (>= size with ZERO_PAGE, and for an adopted anonymous one)
+    explicit MappedFile(const char* path, unsigned options = 0);
+    // Adopts an anonymous mapping of `reserved` bytes holding `content` bytes of text.
+    MappedFile(char* anonymous, size_t reserved, size_t content) : data(anonymous), size(content), mapped(reserved) {}
+    MappedFile(MappedFile&& o) noexcept : fd(o.fd), data(o.data), size(o.size), mapped(o.mapped) { o.fd = -1; o.data = nullptr; o.size = o.mapped = 0; }
+    ~MappedFile();
+    MappedFile(const MappedFile&) = delete;
+    MappedFile& operator=(const MappedFile&) = delete;
+    const uint8_t* bytes() const { return reinterpret_cast<const uint8_t*>(data); }
+};
+
 // The sequences of one window, found by the host (TextSource::next_parsed): each segment is the work of one thread,
 // `seq_bytes` bytes of sequences back to back at seqs[seq_at ...) and n_records + 1 byte offsets, relative to the
 // segment's first sequence, at offsets[off_at ...).

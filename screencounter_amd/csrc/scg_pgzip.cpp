@@ -6,13 +6,13 @@
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
-#include <dlfcn.h>
 #include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
 #include <zlib.h>
 
+#include "scg_gzip.h"
 #include "scg_pgzip.h"
 
 namespace scg {
@@ -33,33 +33,17 @@ uint32_t zlib_crc(uint32_t c, const void* p, size_t n) {
     return c;
 }
 crc_fn pick_crc() {
-    const char* e = std::getenv("SCG_LIBDEFLATE");
-    if (!(e && *e == '0')) {
-        if (void* h = ::dlopen("libdeflate.so.0", RTLD_NOW | RTLD_LOCAL)) {
-            if (void* f = ::dlsym(h, "libdeflate_crc32")) return reinterpret_cast<crc_fn>(f);
-        }
-    }
-    return zlib_crc;
+    const gz::Libdeflate* L = gz::libdeflate();
+    return L && L->crc32 ? L->crc32 : zlib_crc;
 }
 
-// A gzip member header at d[off ...) (RFC 1952): the offset of its DEFLATE stream, or 0 for anything but a header in
-// the form `gzip` writes (optional name, comment and extra field; a header CRC or reserved flags are left to zlib).
+// A gzip member header at d[off ...): the offset of its DEFLATE stream, or 0 for anything but a header in the form `gzip`
+// writes (optional name, comment and extra field; a header CRC or reserved flags are left to zlib) with a trailer's eight
+// bytes at least behind it.
 size_t member_payload(const uint8_t* d, size_t size, size_t off) {
-    if (off > size || size - off < 18 || d[off] != 0x1f || d[off + 1] != 0x8b || d[off + 2] != 8) return 0;
-    const uint8_t flg = d[off + 3];
-    if (flg & 0xE2) return 0;
-    size_t p = off + 10;
-    if (flg & 4) {
-        if (p + 2 > size) return 0;
-        p += 2 + (d[p] | (static_cast<size_t>(d[p + 1]) << 8));
-    }
-    for (int bit : {8, 16}) {                                   // FNAME, FCOMMENT: zero-terminated
-        if (flg & bit) {
-            while (p < size && d[p]) ++p;
-            ++p;
-        }
-    }
-    return p + 8 <= size ? p : 0;
+    gz::MemberHeader h;
+    if (!gz::parse_member_header(d, size, off, h) || (h.flags & 0xE2) || size - h.payload < 8) return 0;
+    return h.payload;
 }
 
 // A run of a chunk's symbols that belongs to one member; `ends`: the member ends with it (trailer values attached).
@@ -227,7 +211,7 @@ struct ParallelGunzip::Impl {
         uint16_t* out = c.buf + WINDOW;
         const uint64_t stop_at = static_cast<uint64_t>(std::min(size, (j + 1) * chunk_bytes)) * 8u;
         std::unique_ptr<Tables> T(new Tables);
-        uint8_t lens[320];
+        uint8_t lens[scginf::LENS_BYTES];
         Bits br;
         uint64_t bit = start;
         size_t member_from = 0;              // where the current member's symbols begin (0: before the chunk, or at its start)
@@ -256,8 +240,8 @@ struct ParallelGunzip::Impl {
                 if (t + 8 > size) { c.failed = true; break; }
                 Segment s;
                 s.from = member_from; s.to = c.n; s.ends = true;
-                s.crc = data[t] | (uint32_t(data[t + 1]) << 8) | (uint32_t(data[t + 2]) << 16) | (uint32_t(data[t + 3]) << 24);
-                s.isize = data[t + 4] | (uint32_t(data[t + 5]) << 8) | (uint32_t(data[t + 6]) << 16) | (uint32_t(data[t + 7]) << 24);
+                const gz::Trailer tr = gz::read_trailer(data + t);
+                s.crc = tr.crc; s.isize = tr.isize;
                 c.segs.push_back(s);
                 bit = static_cast<uint64_t>(t + 8) * 8u;
                 in_member = false;
@@ -279,7 +263,7 @@ struct ParallelGunzip::Impl {
         const uint64_t from = static_cast<uint64_t>(j * chunk_bytes) * 8u;
         const uint64_t to = static_cast<uint64_t>(std::min(size, (j + 1) * chunk_bytes)) * 8u;
         std::unique_ptr<Tables> T(new Tables);
-        uint8_t lens[320];
+        uint8_t lens[scginf::LENS_BYTES];
         uint64_t at = from;
         for (int tries = 0; tries < 4; ++tries) {
             const uint64_t s = find_dynamic_block(data, size, at, to, *T, lens);

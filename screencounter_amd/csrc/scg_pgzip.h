@@ -27,6 +27,15 @@
 // This header holds the single-threaded pieces (bit reader, table builder, marker-mode block decoder, block finder);
 // plain C++ so that tests/pgzip_harness.cpp can run them against zlib under AddressSanitizer.  scg_pgzip.cpp holds
 // the threads.
+//
+// RULES live in scg_inflate.h, SPEED and LAYOUT here.  What zlib accepts -- a block header's limits and code-length code
+// (read_code_lengths), when a set of code lengths is a code (code_set_allowed), the fixed code, the bases and extra bits of
+// length and distance symbols, the marker values -- is stated once, there, for the device decoders and for this one: this
+// decoder takes what the device's hands back, and the two must judge a stream alike.  One exception, by measurement:
+// find_dynamic_block's cheap filter has a second spelling in gunzip_find_kernel (scg_inflate.h, "dynamic block filter").
+// Kept here is what is tuned for a host core: the two-level 11/8-bit tables and build_table's filling of them, decode_block's
+// loop, and a copy_match that may write 15 symbols beyond the match (scginf::copy_match writes none).  Each reader keeps its
+// own overrun() and slack (IN_SLACK 16 here, 64 there): contracts of a buffer, not rules of the format.
 #ifndef SCG_PGZIP_H
 #define SCG_PGZIP_H
 
@@ -34,11 +43,13 @@
 #include <cstdint>
 #include <cstring>
 
+#include "scg_inflate.h"
+
 namespace scg {
 namespace pgz {
 
-constexpr uint32_t WINDOW = 32768;              // DEFLATE's history
-constexpr uint16_t MARKER = 0x8000;             // symbol MARKER + k = byte k of the unknown window (k = 0 oldest)
+constexpr uint32_t WINDOW = scginf::MARKER_WINDOW;   // DEFLATE's history
+using scginf::MARKER;                           // symbol MARKER + k = byte k of the unknown window (k = 0 oldest)
 constexpr int LIT_BITS = 11;                    // primary table of the literal/length code
 constexpr int DIST_BITS = 8;                    // primary table of the distance code
 constexpr size_t IN_SLACK = 16;                 // bytes that must be readable beyond the end of the compressed data
@@ -93,17 +104,16 @@ struct Bits {
     }
     uint32_t peek(uint32_t n) const { return static_cast<uint32_t>(buf) & ((1u << n) - 1u); }
     void drop(uint32_t n) { buf >>= n; cnt -= n; }
-    uint32_t take(uint32_t n) { const uint32_t v = peek(n); drop(n); return v; }
+    uint32_t bits(uint32_t n) { const uint32_t v = peek(n); drop(n); return v; }
     uint64_t bitpos() const { return static_cast<uint64_t>(pos) * 8u - cnt; }
     bool overrun() const { return bitpos() > static_cast<uint64_t>(size) * 8u; }
 };
 
-// Canonical Huffman code -> two-level decoding table.  Rules as in zlib's inflate_table: an over-subscribed set is
-// rejected; an incomplete one too, except a literal/length or distance code whose only code has one bit
-// (`allow_single`).  Returns false for a set zlib rejects.
+// Canonical Huffman code of a literal/length or distance alphabet -> two-level decoding table.  Returns false for a set
+// of lengths zlib rejects (scginf::code_set_allowed).
 //   kind_of(symbol, &extra, &payload) gives the entry kind of a symbol.
 template<class KindOf>
-inline bool build_table(const uint8_t* lens, int n, int tbits, uint32_t* table, size_t cap, bool allow_single, KindOf kind_of) {
+inline bool build_table(const uint8_t* lens, int n, int tbits, uint32_t* table, size_t cap, KindOf kind_of) {
     uint16_t count[16] = {0};
     for (int s = 0; s < n; ++s) ++count[lens[s]];
     count[0] = 0;
@@ -112,13 +122,7 @@ inline bool build_table(const uint8_t* lens, int n, int tbits, uint32_t* table, 
     const size_t primary = size_t(1) << tbits;
     for (size_t i = 0; i < primary; ++i) table[i] = 0;
     if (maxlen < 1) return true;                        // no codes: every lookup fails, which is zlib's error when one is used
-    int left = 1;
-    for (int l = 1; l <= 15; ++l) {
-        left <<= 1;
-        left -= count[l];
-        if (left < 0) return false;
-    }
-    if (left > 0 && !(allow_single && maxlen == 1)) return false;
+    if (!scginf::code_set_allowed(count, maxlen, 1)) return false;
     uint16_t next[16];
     {
         uint32_t code = 0;
@@ -154,88 +158,39 @@ inline bool build_table(const uint8_t* lens, int n, int tbits, uint32_t* table, 
 }
 
 inline uint32_t litlen_kind(int s, uint32_t& extra, uint32_t& payload) {
-    static const uint16_t base[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
-    static const uint8_t ext[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
     if (s < 256) { payload = static_cast<uint32_t>(s); return K_LITERAL; }
     if (s == 256) return K_END;
     if (s > 285) return K_INVALID;                      // 286, 287 take part in the fixed code but never occur ("invalid literal/length code")
-    extra = ext[s - 257]; payload = base[s - 257];
+    extra = scginf::length_extra(static_cast<uint32_t>(s) - 257u);
+    payload = scginf::length_base(static_cast<uint32_t>(s) - 257u, extra);
     return K_LENGTH;
 }
 inline uint32_t dist_kind(int s, uint32_t& extra, uint32_t& payload) {
-    static const uint16_t base[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145,
-                                      8193, 12289, 16385, 24577};
-    static const uint8_t ext[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
     if (s > 29) return K_INVALID;                       // "invalid distance code"
-    extra = ext[s]; payload = base[s];
+    extra = scginf::dist_extra(static_cast<uint32_t>(s));
+    payload = scginf::dist_base(static_cast<uint32_t>(s), extra);
     return K_DIST;
 }
 
 enum : int { BLOCK_OK = 0, BLOCK_FINAL = 1, BLOCK_BAD = -1, BLOCK_FULL = -2 };
 
-// Reads a dynamic block's code lengths (the bits behind the 3-bit block header) and builds both tables.
-// lens: scratch of 320 bytes.  Every rule of zlib's inflate for this part of the stream (inflate.c: TABLE .. CODELENS).
+// Reads a dynamic block's code lengths (the bits behind the 3-bit block header: scginf::read_code_lengths, with zlib's
+// rules for them) and builds both tables.  lens: scratch of scginf::LENS_BYTES.
 inline bool read_dynamic_header(Bits& br, Tables& T, uint8_t* lens) {
+    uint16_t cltab[1 << scginf::CL_BITS], count[16], sym[19], offs[16];      // the code-length code
+    int nlen, ndist;
     br.refill();
-    const int nlen = static_cast<int>(br.take(5)) + 257;
-    const int ndist = static_cast<int>(br.take(5)) + 1;
-    const int ncode = static_cast<int>(br.take(4)) + 4;
-    if (nlen > 286 || ndist > 30) return false;                          // "too many length or distance symbols"
-    static const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-    uint8_t cl[19] = {0};
-    for (int i = 0; i < ncode; ++i) {
-        if ((i & 15) == 0) br.refill();
-        cl[order[i]] = static_cast<uint8_t>(br.take(3));
-    }
-    // the code-length code: 7-bit table, never longer
-    uint32_t cltab[128];
-    int left = 1;
-    {
-        uint16_t count[8] = {0};
-        for (int i = 0; i < 19; ++i) ++count[cl[i]];
-        count[0] = 0;
-        for (int l = 1; l <= 7; ++l) { left <<= 1; left -= count[l]; if (left < 0) return false; }
-        if (left > 0) return false;                                      // "invalid code lengths set" (incomplete sets are not allowed here)
-    }
-    if (!build_table(cl, 19, 7, cltab, 128, false, [](int s, uint32_t&, uint32_t& payload) { payload = static_cast<uint32_t>(s); return uint32_t(K_LITERAL); })) return false;
-    int have = 0;
-    while (have < nlen + ndist) {
-        br.refill();
-        if (br.overrun()) return false;
-        const uint32_t e = cltab[br.peek(7)];
-        if (e_kind(e) != K_LITERAL) return false;
-        br.drop(e_bits(e));
-        const int s = static_cast<int>(e_payload(e));
-        if (s < 16) { lens[have++] = static_cast<uint8_t>(s); continue; }
-        uint8_t fill = 0;
-        int rep;
-        if (s == 16) {
-            if (have == 0) return false;                                 // "invalid bit length repeat"
-            fill = lens[have - 1];
-            rep = 3 + static_cast<int>(br.take(2));
-        } else if (s == 17) {
-            rep = 3 + static_cast<int>(br.take(3));
-        } else {
-            rep = 11 + static_cast<int>(br.take(7));
-        }
-        if (have + rep > nlen + ndist) return false;                     // "invalid bit length repeat"
-        while (rep--) lens[have++] = fill;
-    }
-    if (lens[256] == 0) return false;                                    // "invalid code -- missing end-of-block"
-    if (!build_table(lens, nlen, LIT_BITS, T.lit, LIT_TABLE, true, litlen_kind)) return false;          // "invalid literal/lengths set"
-    if (!build_table(lens + nlen, ndist, DIST_BITS, T.dist, DIST_TABLE, true, dist_kind)) return false;  // "invalid distances set"
+    if (!scginf::read_code_lengths(br, lens, nlen, ndist, cltab, count, sym, offs)) return false;
+    if (!build_table(lens, nlen, LIT_BITS, T.lit, LIT_TABLE, litlen_kind)) return false;          // "invalid literal/lengths set"
+    if (!build_table(lens + nlen, ndist, DIST_BITS, T.dist, DIST_TABLE, dist_kind)) return false;  // "invalid distances set"
     return true;
 }
 
 inline void fixed_tables(Tables& T) {
     uint8_t lens[320];
-    for (int s = 0; s < 144; ++s) lens[s] = 8;
-    for (int s = 144; s < 256; ++s) lens[s] = 9;
-    for (int s = 256; s < 280; ++s) lens[s] = 7;
-    for (int s = 280; s < 288; ++s) lens[s] = 8;
-    for (int s = 0; s < 32; ++s) lens[288 + s] = 5;
-    build_table(lens, 288, LIT_BITS, T.lit, LIT_TABLE, true, litlen_kind);
-    build_table(lens + 288, 32, DIST_BITS, T.dist, DIST_TABLE, true, dist_kind);     // (codes 30, 31 decode to K_INVALID)
+    scginf::fixed_code_lengths(lens);
+    build_table(lens, 288, LIT_BITS, T.lit, LIT_TABLE, litlen_kind);
+    build_table(lens + 288, 32, DIST_BITS, T.dist, DIST_TABLE, dist_kind);     // (codes 30, 31 decode to K_INVALID)
 }
 
 // out[0 .. n) = out[-dist .. ), overlapping the way LZ77 means it; may write up to 15 symbols beyond n.
@@ -268,13 +223,13 @@ template<bool COUNT = false>
 inline int decode_block(Bits& br, Tables& T, uint16_t* out, size_t& op, size_t cap, size_t reach, uint8_t* lens, size_t* n_symbols = nullptr) {
     br.refill();
     if (br.overrun()) return BLOCK_BAD;
-    const uint32_t last = br.take(1);
-    const uint32_t type = br.take(2);
+    const uint32_t last = br.bits(1);
+    const uint32_t type = br.bits(2);
     if (type == 3) return BLOCK_BAD;                                     // "invalid block type"
     if (type == 0) {
         br.drop(br.cnt & 7u);                                            // to the byte boundary
         br.refill();
-        const uint32_t n = br.take(16), nn = br.take(16);
+        const uint32_t n = br.bits(16), nn = br.bits(16);
         if ((n ^ 0xFFFFu) != nn) return BLOCK_BAD;                       // "invalid stored block lengths"
         if (n > cap - op) return BLOCK_FULL;
         const uint64_t at = br.bitpos();                                 // byte aligned

@@ -2,6 +2,7 @@
 // the scheduling of many files over them, and the shaping of counters into the reference's outputs: one reader per kind
 // of result (result_counts, result_combinations, result_diagnostics), shared by the plan, one-file and many-files entries.
 #include "scg_internal.hpp"
+#include "scg_gzip.h"
 
 namespace scgapi {
 
@@ -98,8 +99,7 @@ uint64_t text_bytes_hint(const char* path) {
     FILE* f = std::fopen(path, "rb");
     size_t got = 0;
     if (f) { got = std::fread(h, 1, 2, f); std::fclose(f); }
-    const bool gz = got == 2 && h[0] == 0x1f && h[1] == 0x8b;
-    return static_cast<uint64_t>(st.st_size) * (gz ? 5 : 1);
+    return static_cast<uint64_t>(st.st_size) * (got == 2 && scg::gz::is_gzip(h) ? 5 : 1);
 }
 
 // A second plan with the same compiled (host-side) content, for another device.  Call before to_device().

@@ -10,6 +10,7 @@
 // bytes, u8 valid, the stream, the text (little endian).  Each runs through ours(): accept / reject must equal zlib's verdict
 // and the entry's flag, and accepted text must equal the entry's.
 #include "../screencounter_amd/csrc/scg_inflate.h"
+#include "../screencounter_amd/csrc/scg_pgzip.h"
 
 #include <zlib.h>
 
@@ -175,10 +176,30 @@ static int lanes_model(const uint8_t* in, uint32_t in_len, OutT* out, uint32_t o
     return INFLATE_OK;
 }
 
+// The host's chunk decoder (scg_pgzip.h: its own tables and loop over the same rules), block after block from the member's
+// first bit with nothing in front (reach 0).  Accepted only if the last block is final, the stream ends in the input's
+// last byte and the text has exactly n symbols.  out: n + 16 symbols (the slack pgz::copy_match announces); in: size +
+// pgz::IN_SLACK bytes.
+static bool host_chunk_decoder(const uint8_t* in, size_t size, uint16_t* out, size_t n) {
+    using namespace scg::pgz;
+    static Tables T;
+    uint8_t lens[scginf::LENS_BYTES];
+    Bits br;
+    uint64_t bit = 0;
+    size_t op = 0;
+    int rc;
+    do {
+        br.open(in, size, bit);
+        rc = decode_block(br, T, out, op, n, 0, lens);
+        bit = br.bitpos();
+    } while (rc == BLOCK_OK);
+    return rc == BLOCK_FINAL && ((bit + 7) >> 3) == size && op == n;
+}
+
 // The decoder with "wavefronts" of 1, 7 and 64 lanes (the device runs 64): all must agree, byte for byte and verdict
 // for verdict -- the wider ones exercise the batched literals and the deferred stores of short matches.  So must the model
 // of the lane-parallel decoder, in bytes and -- whatever is accepted -- in symbols, where no marker may appear: nothing
-// reaches in front of a member's start.
+// reaches in front of a member's start.  And so must the host's chunk decoder, which takes what the device hands back.
 static int ours(const std::vector<uint8_t>& c, size_t n, std::vector<uint8_t>& out) {
     // exact-size buffers so that ASan sees any access beyond the slack or the output
     std::vector<uint8_t> in(c.size() + scginf::IN_SLACK, 0xA5);
@@ -209,6 +230,17 @@ static int ours(const std::vector<uint8_t>& c, size_t n, std::vector<uint8_t>& o
         for (size_t i = 0; same && i < n; ++i) same = os[i] == out[i];             // (a marker is >= 0x8000: no byte)
         if (!same) {
             fprintf(stderr, "FAIL the lane-parallel model in symbols: rc %d, or symbols that are not the text\n", rcs);
+            exit(1);
+        }
+    }
+    {
+        std::vector<uint8_t> hin(c.size() + scg::pgz::IN_SLACK, 0xA5);
+        memcpy(hin.data(), c.data(), c.size());
+        std::vector<uint16_t> hs(n + 16, 0xEEEE);
+        bool same = host_chunk_decoder(hin.data(), c.size(), hs.data(), n) == ok;
+        for (size_t i = 0; ok && same && i < n; ++i) same = hs[i] == out[i];        // (no symbol above 255: no marker)
+        if (!same) {
+            fprintf(stderr, "FAIL the host chunk decoder disagrees with the wavefront decoder's rc %d, or its symbols are not the text\n", rc);
             exit(1);
         }
     }

@@ -111,6 +111,33 @@ def test_header_fields(harness, tmp_path):
     assert run(harness, p).startswith("declined ok")
 
 
+def test_truncated_headers_are_declined(harness, tmp_path):
+    """A member header that the file cuts short is no header for this decoder, wherever the cut falls -- as the file's
+    first member (of any size: both sides of the 18 bytes the smallest member takes) and behind a complete one."""
+    raw = gz(TEXT[:50000], 6)
+    body = raw[10:]
+
+    def header(flags):
+        h = bytearray(raw[:10])
+        h[3] = flags
+        return bytes(h)
+
+    cut = {
+        "inside XLEN": header(4) + b"\x05",
+        "inside the extra field": header(4) + (100).to_bytes(2, "little") + b"x" * 20,
+        "XLEN beyond the file": header(4) + (65535).to_bytes(2, "little") + body,
+        "inside the name": header(8) + b"a_name_without_its_end.fastq",
+        "inside the comment": header(8 | 16) + b"name\0" + b"a comment without its end",
+        "7 bytes behind the payload": header(8) + b"name\0" + body[:7],
+        "0 bytes behind the payload": header(4 | 8) + (3).to_bytes(2, "little") + b"abc" + b"name\0",
+    }
+    p = str(tmp_path / "cut.gz")
+    for what, data in cut.items():
+        for front in (b"", raw):
+            open(p, "wb").write(front + data)
+            assert run(harness, p).startswith("declined"), (what, len(front))
+
+
 def test_tiny_and_empty(harness, tmp_path):
     p = str(tmp_path / "t.gz")
     open(p, "wb").write(gz(b"@r\nACGT\n+\nIIII\n"))       # one fixed-Huffman block

@@ -5,6 +5,7 @@
 #include <memory>
 #include <vector>
 
+#include "../screencounter_amd/csrc/scg_gzip.h"
 #include "../screencounter_amd/csrc/scg_pgzip.h"
 
 using namespace scg::pgz;
@@ -22,16 +23,12 @@ int main(int argc, char** argv) {
     file.resize(size + 64, 0);
     std::vector<uint16_t> out(WINDOW + (size_t(1) << 26));
     std::unique_ptr<Tables> T(new Tables);
-    uint8_t lens[320];
+    uint8_t lens[scginf::LENS_BYTES];
     size_t symbols = 0, text = 0, members = 0, off = 0;
-    while (off + 18 <= size && file[off] == 0x1f && file[off + 1] == 0x8b) {
-        size_t p = off + 10;
-        const uint8_t flg = file[off + 3];
-        if (flg & 4) p += 2 + (file[p] | (size_t(file[p + 1]) << 8));
-        for (int bit : {8, 16}) if (flg & bit) { while (file[p]) ++p; ++p; }
-        if (flg & 2) p += 2;
+    scg::gz::MemberHeader h;
+    while (off + 18 <= size && scg::gz::parse_member_header(file.data(), size, off, h)) {       // (any flags: a header CRC is skipped, not checked)
         Bits br;
-        uint64_t bit = uint64_t(p) * 8;
+        uint64_t bit = uint64_t(h.payload) * 8;
         size_t op = 0;
         int rc;
         do {
