@@ -92,8 +92,7 @@ struct ScratchLease {
     ScratchLease(int device, size_t in_bytes, size_t sym_bytes) {
         {
             std::lock_guard<std::mutex> g(scratch_mu);
-            const char* e = std::getenv("SCG_BUFFER_CACHE");
-            if (!scratch_cache.busy && !(e && *e == '0')) { scratch_cache.busy = true; cached = true; }
+            if (!scratch_cache.busy && env().buffer_cache) { scratch_cache.busy = true; cached = true; }
         }
         s = cached ? &scratch_cache : &local;
         try {
@@ -165,18 +164,16 @@ public:
 
     // The header, the sizes, and the first group.  False: not a file for this decoder.
     bool begin() {
-        const bool test_hook = std::getenv("SCG_DGZIP_CHUNK_KB") != nullptr;       // (tiny chunks, tiny files)
-        if (!f.data || f.size < (test_hook ? size_t(64) : size_t(2) << 20)) return false;
-        chunk_bytes = size_t(64) << 10;          // (MI355X, 8 M reads: 128 KB 131 Mreads/s, 64 KB 139, 32 KB 120)
-        if (const char* e = std::getenv("SCG_DGZIP_CHUNK_KB")) { const long kb = std::atol(e); if (kb >= 4) chunk_bytes = static_cast<size_t>(kb) << 10; }
-        if (const char* e = std::getenv("SCG_DGZIP_TAIL_GROUP")) tail_group = static_cast<uint32_t>(std::max(1L, std::atol(e)));   // (tests: many groups in small files)
-        if (const char* e = std::getenv("SCG_DGZIP_MIN_MEMBER_CHUNKS")) min_member_chunks = static_cast<uint64_t>(std::max(0L, std::atol(e)));   // (tests: members of any size)
+        const Env& sw = env();                   // the SCG_DGZIP_* test hooks: tiny chunks, tiny files, many groups, members of any size
+        if (!f.data || f.size < (sw.dgzip_tiny ? size_t(64) : size_t(2) << 20)) return false;
+        chunk_bytes = sw.dgzip_chunk_kb << 10;   // 64 KB (MI355X, 8 M reads: 128 KB 131 Mreads/s, 64 KB 139, 32 KB 120)
+        tail_group = sw.dgzip_tail_group;
+        min_member_chunks = sw.dgzip_min_member_chunks;
         if (!member_at(0)) return false;
         // a chunk decodes from its block start to the next chunk's: up to two chunks of input when a neighbour holds no block start
         // (a DEFLATE block is 30-60 KB of compressed bytes as a rule: small chunks -- the tests' -- mostly hold no block start at all)
         cap_syms = std::max<uint64_t>(chunk_bytes * 16, uint64_t(1) << 20) + 65536;
-        uint64_t group_bytes = uint64_t(512) << 20;                     // (its text must stay below 4 GB: the CRC pieces are indexed with 32 bits)
-        if (const char* e = std::getenv("SCG_DGZIP_GROUP_KB")) { const long kb = std::atol(e); if (kb >= 4) group_bytes = static_cast<uint64_t>(kb) << 10; }
+        const uint64_t group_bytes = sw.dgzip_group_kb << 10;           // 512 MB (its text must stay below 4 GB: the CRC pieces are indexed with 32 bits)
         group_chunks = std::max<uint64_t>(1, group_bytes / chunk_bytes);
         return next_group();
     }
@@ -428,8 +425,7 @@ void release_device_gunzip_scratch() {
 }
 
 std::unique_ptr<TextSource> TextSource::open_on_device(const char* path, int device, int threads) {
-    const char* e = std::getenv("SCG_DEVICE_GUNZIP");
-    if (e && *e == '0') return nullptr;
+    if (!env().device_gunzip) return nullptr;
     std::unique_ptr<DeviceGunzipSource> s(new DeviceGunzipSource(path, device, threads));
     if (!s->begin()) return nullptr;
     return std::unique_ptr<TextSource>(s.release());

@@ -12,6 +12,7 @@
 //   - "line numbers" in messages advance by exactly four per record, as the reference counts them.
 // Unlike the reference's byte-at-a-time virtual-call loop this scanner works on large buffers
 // with memchr, and only the sequence bytes are kept (names and qualities never leave this file).
+#include "scg_env.h"
 #include "scg_gzip.h"
 #include "scg_host.h"
 #include "scg_ingest.h"
@@ -221,11 +222,7 @@ static int cpu_share() {
 int default_host_threads(int requested, int devices) {
     // R's num.threads defaults to 1 and is advisory; the stager sizes itself from the machine -- sixteen threads per
     // device the call feeds, within the CPUs the process may use -- unless SCG_HOST_THREADS says otherwise.
-    const char* env = std::getenv("SCG_HOST_THREADS");
-    if (env && *env) {
-        int v = std::atoi(env);
-        if (v >= 1) return v;
-    }
+    if (env().host_threads >= 1) return env().host_threads;
     static const int share = cpu_share();
     int n = std::min(share, 16 * std::max(1, devices));
     if (n > 64) n = 64;
@@ -291,11 +288,7 @@ ParallelFastq::ParallelFastq(const char* path, int nthreads) : impl(new Impl) {
         impl->data = static_cast<const char*>(m);
     }
     impl->nthreads = nthreads < 1 ? 1 : nthreads;
-    size_t piece = size_t(32) << 20;
-    if (const char* env = std::getenv("SCG_FASTQ_PIECE_KB")) {      // test hook: tiny pieces force many hand-overs
-        long kb = std::atol(env);
-        if (kb > 0) piece = static_cast<size_t>(kb) << 10;
-    }
+    const size_t piece = env().fastq_piece_kb << 10;      // 32 MB; test hook: tiny pieces force many hand-overs
     impl->window = static_cast<size_t>(impl->nthreads) * piece;
     // the file must open with a strict record for this reader to apply at all
     if (impl->size && !impl->record_end(0)) impl->odd = true;

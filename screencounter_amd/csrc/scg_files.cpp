@@ -143,7 +143,6 @@ bool is_parallel_gzip(const scg::TextSource* s) { return s && std::strcmp(s->kin
 
 // What the two ladders share: the rung they stand on, and what a decline does to the plans.
 struct Ladder {
-    const Switches sw;
     int rung = 0;
     bool traced;
     std::vector<int> devices;     // of the call; cut down to those the rung in use works on
@@ -157,7 +156,7 @@ struct Ladder {
         if (!scg::TextSource::ordinary_gzip(path, threads)) return nullptr;
         std::unique_ptr<scg::TextSource> s = scg::TextSource::open_on_device(path, devices[0], threads);
         if (!s && traced) std::fprintf(stderr, "[scg] rung device-gunzip: declined -> host-threads\n");
-        if (!s && sw.gunzip_strict) throw Error(SCG_ERR_UNSUPPORTED, "the device gzip decoder handed the file back (SCG_DEVICE_GUNZIP=2 forbids the fall-back)");
+        if (!s && scg::env().gunzip_strict) throw Error(SCG_ERR_UNSUPPORTED, "the device gzip decoder handed the file back (SCG_DEVICE_GUNZIP=2 forbids the fall-back)");
         return s;
     }
     // `plans`: null while they do not exist yet
@@ -176,7 +175,7 @@ struct SingleEndLadder : Ladder {
     enum Rung { DEVICE_GUNZIP, DEVICE_INFLATE, HOST_THREADS, SINGLE_STREAM, HOST_READER };
 
     SingleEndLadder(const char* file, scg::FastqStream& stream, int n_threads, bool one_file) : path(file), fq(stream), nthreads(n_threads) {
-        rung = !sw.device_scan ? HOST_READER : one_file ? DEVICE_GUNZIP : DEVICE_INFLATE;
+        rung = !scg::env().device_scan ? HOST_READER : one_file ? DEVICE_GUNZIP : DEVICE_INFLATE;
     }
 
     // The first rung that applies takes its first windows; no plan is needed for that.
@@ -228,7 +227,7 @@ private:
             devices.resize(1);
             break;
         case DEVICE_INFLATE:
-            if (!sw.device_inflate) return false;
+            if (!scg::env().device_inflate) return false;
             src = scg::TextSource::open(path, threads);
             if (!src->has_members()) return false;           // (the source serves HOST_THREADS)
             inflate = true;
@@ -243,7 +242,7 @@ private:
             break;
         }
         entered(name(rung));
-        ring.reset(new WindowRing(*src, devices, sw, inflate));
+        ring.reset(new WindowRing(*src, devices, inflate));
         devices.resize(ring->n_devices());
         return true;
     }
@@ -252,7 +251,7 @@ private:
         ring.reset();
         src.reset();
         const int next = rung < HOST_THREADS ? HOST_THREADS : rung == HOST_THREADS && parallel_gzip ? SINGLE_STREAM : HOST_READER;
-        declined(name(rung), name(next), rung == DEVICE_INFLATE && sw.inflate_strict, plans);
+        declined(name(rung), name(next), rung == DEVICE_INFLATE && scg::env().inflate_strict, plans);
         rung = next;
     }
 };
@@ -281,7 +280,7 @@ std::unique_ptr<PlanSet> compile_and_finish(L& ladder, const Compile& compile, c
     return set;
 }
 
-size_t whole_text_window(const Switches& sw) { return window_bytes(sw, TEXT_WINDOW, ~uint64_t(0) >> 8); }
+size_t whole_text_window() { return window_bytes(TEXT_WINDOW, ~uint64_t(0) >> 8); }
 
 // One single-end file on a set of plans (one per device), for the many-files entries.
 void count_single_end(const std::vector<scg_plan*>& plans, const char* path, scg::FastqStream& fq, int nthreads) {
@@ -295,7 +294,7 @@ void count_single_end(const std::vector<scg_plan*>& plans, const char* path, scg
 std::unique_ptr<PlanSet> compile_and_count_single_end(const char* path, scg::FastqStream& fq, int nthreads, Compile compile) {
     SingleEndLadder ladder(path, fq, nthreads, true);
     return compile_and_finish(ladder, compile, [&] {
-        ladder.devices = devices_for_input(text_bytes_hint(path), whole_text_window(ladder.sw));
+        ladder.devices = devices_for_input(text_bytes_hint(path), whole_text_window());
         ladder.threads = scg::default_host_threads(nthreads, static_cast<int>(ladder.devices.size()));
         ladder.begin();
     }, "compile + first window", "count file");
@@ -386,7 +385,7 @@ struct PairedLadder : Ladder {
 
     PairedLadder(const char* file1, const char* file2, scg::FastqStream& stream1, scg::FastqStream& stream2, int n_threads)
         : path1(file1), path2(file2), fq1(stream1), fq2(stream2), nthreads(n_threads) {
-        rung = sw.device_scan ? DEVICE_MATES : HOST_READER;
+        rung = scg::env().device_scan ? DEVICE_MATES : HOST_READER;
     }
 
     // The first rung that applies takes the first window of each file; no plan is needed for that.
@@ -448,22 +447,22 @@ private:
             s2 = open_mate(path2, rung == DEVICE_MATES);
         }
         if (rung == DEVICE_MATES) {
-            const bool inflates = sw.device_inflate && (s1->has_members() || s2->has_members());
+            const bool inflates = scg::env().device_inflate && (s1->has_members() || s2->has_members());
             if (!inflates && !s1->device_resident() && !s2->device_resident()) return false;      // (the sources serve HOST_THREADS)
         }
         if (rung == HOST_THREADS) parallel_gzip = is_parallel_gzip(s1.get()) || is_parallel_gzip(s2.get());
         entered(name(rung));
-        if (rung == HOST_THREADS && devices.size() > 1 && s1->parses() && s2->parses() && sw.host_scan) {
-            rounds.reset(new PairedRounds(devices, *s1, *s2, sw));
+        if (rung == HOST_THREADS && devices.size() > 1 && s1->parses() && s2->parses() && scg::env().host_scan) {
+            rounds.reset(new PairedRounds(devices, *s1, *s2));
         } else {
             devices.resize(1);
-            pipe.reset(new PairedPipeline(devices[0], *s1, *s2, sw, rung == DEVICE_MATES));
+            pipe.reset(new PairedPipeline(devices[0], *s1, *s2, rung == DEVICE_MATES));
         }
         return true;
     }
 
     void decline(const std::vector<scg_plan*>* plans) {
-        const bool strict = rung == DEVICE_MATES && sw.inflate_strict && pipe && pipe->inflates();
+        const bool strict = rung == DEVICE_MATES && scg::env().inflate_strict && pipe && pipe->inflates();
         pipe.reset();
         rounds.reset();
         s1.reset();
@@ -488,7 +487,7 @@ std::unique_ptr<PlanSet> compile_and_count_paired(const char* path1, const char*
                                                   Compile compile) {
     PairedLadder ladder(path1, path2, fq1, fq2, nthreads);
     return compile_and_finish(ladder, compile, [&] {
-        ladder.devices = devices_for_input(text_bytes_hint(path1) + text_bytes_hint(path2), whole_text_window(ladder.sw));
+        ladder.devices = devices_for_input(text_bytes_hint(path1) + text_bytes_hint(path2), whole_text_window());
         ladder.threads = scg::default_host_threads(nthreads, static_cast<int>(ladder.devices.size()));
         ladder.begin();
     }, "compile + first windows", "count files");

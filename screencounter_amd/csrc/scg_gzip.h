@@ -14,6 +14,8 @@
 #include <dlfcn.h>
 #include <initializer_list>
 
+#include "scg_env.h"
+
 namespace scg {
 namespace gz {
 
@@ -81,7 +83,7 @@ inline Trailer read_trailer(const uint8_t* p) { return Trailer{le32(p), le32(p +
 
 // libdeflate (whole-buffer DEFLATE at 2-3 x zlib's inflate, CRC-32 by carry-less multiplication at ~10 GB/s) is part of
 // the image as a shared library without headers: looked up at run time, once, and never unloaded.  Null when the library
-// is absent or SCG_LIBDEFLATE=0 (read at every call, before any look-up); a function the library lacks is null.
+// is absent or SCG_LIBDEFLATE=0 (asked at every call, before any look-up); a function the library lacks is null.
 struct Libdeflate {
     void* (*alloc)() = nullptr;
     void (*release)(void*) = nullptr;
@@ -89,8 +91,7 @@ struct Libdeflate {
     uint32_t (*crc32)(uint32_t, const void*, size_t) = nullptr;
 };
 inline const Libdeflate* libdeflate() {
-    const char* e = std::getenv("SCG_LIBDEFLATE");
-    if (e && *e == '0') return nullptr;
+    if (!env().libdeflate) return nullptr;
     static const Libdeflate* const found = []() -> const Libdeflate* {
         void* h = ::dlopen("libdeflate.so.0", RTLD_NOW | RTLD_LOCAL);
         if (!h) return nullptr;

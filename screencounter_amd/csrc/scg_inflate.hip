@@ -21,6 +21,7 @@
 
 #include "scg_inflate.h"
 #include "scg_textscan.h"
+#include "scg_env.h"
 
 namespace {
 
@@ -809,8 +810,7 @@ const CrcPowers& crc_powers() {
 hipError_t launch_inflate_members(const uint8_t* d_in, const InflateMember* d_members, uint32_t n, char* d_text, uint32_t* d_status, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     // SCG_INFLATE_LANES=0: the decoder that walks every symbol with the whole wavefront (measurement / test aid)
-    const char* old_decoder = std::getenv("SCG_INFLATE_LANES");
-    if (old_decoder && *old_decoder == '0') {
+    if (!env().inflate_lanes) {
         hipLaunchKernelGGL(inflate_members_kernel, dim3(n), dim3(INFLATE_BLOCK), 0, stream, d_in, d_members, n,
                            reinterpret_cast<uint8_t*>(d_text), d_status);
     } else {

@@ -1,5 +1,6 @@
 // scg_ingest.cpp -- sources of raw FASTQ text for the device-side record scan (see scg_ingest.h).
 #include "scg_ingest.h"
+#include "scg_env.h"
 #include "scg_host.h"
 #include "scg_pgzip.hpp"
 #include "scg_gzip.h"
@@ -550,8 +551,7 @@ protected:
 std::unique_ptr<MappedFile> inflate_whole(const char* path) {
     const gz::Libdeflate* L = gz::libdeflate();
     if (!L || !L->alloc) return nullptr;
-    size_t limit = size_t(8) << 30;
-    if (const char* e = std::getenv("SCG_GZIP_WHOLE_GB")) limit = static_cast<size_t>(std::max(0.0, std::atof(e)) * double(size_t(1) << 30));
+    const size_t limit = static_cast<size_t>(env().gzip_whole_gb * double(size_t(1) << 30));
     MappedFile in(path);
     // (FASTQ rarely compresses by less than three: a file that large would hit the limit after seconds of wasted work)
     if (limit == 0 || in.size < 18 || in.size > limit / 3) return nullptr;
@@ -590,8 +590,7 @@ class PgzipSource : public CarrySource {
 public:
     PgzipSource(const char* path, int nthreads) : f(path, MappedFile::ZERO_PAGE), pg(f.bytes(), f.size, nthreads) { threads = nthreads; }
     static bool wanted(const char* path, int nthreads) {
-        const char* e = std::getenv("SCG_PGZIP");             // test hook: 0 keeps the single inflate streams
-        if (e && *e == '0') return false;
+        if (!env().pgzip) return false;                       // test hook: 0 keeps the single inflate streams
         struct stat st;
         if (::stat(path, &st) != 0) return false;
         return ParallelGunzip::chunk_size_for(static_cast<size_t>(st.st_size), nthreads) != 0;

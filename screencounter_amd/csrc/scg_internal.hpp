@@ -24,6 +24,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "scg_env.h"
 #include "scg_host.h"
 #include "scg_ingest.h"
 #include "scg_pgzip.hpp"
@@ -49,8 +50,11 @@ inline void copy_err(char* err, size_t cap, const char* msg) {
     }
 }
 
+// Every C entry point that does any work runs its body here: one snapshot of the SCG_* switches for the call
+// (scg_env.h), and every exception turned into a code and a message.
 template<class F>
 inline int guarded(char* err, size_t cap, F f) {
+    const scg::EnvScope call;
     try {
         f();
         if (err && cap) err[0] = '\0';
@@ -74,11 +78,7 @@ inline int guarded(char* err, size_t cap, F f) {
 struct Trace {
     bool on;
     std::chrono::steady_clock::time_point t0, last;
-    Trace() : on(false) {
-        const char* e = std::getenv("SCG_TRACE");
-        on = e && *e && *e != '0';
-        t0 = last = std::chrono::steady_clock::now();
-    }
+    Trace() : on(scg::env().trace) { t0 = last = std::chrono::steady_clock::now(); }
     void mark(const char* what) {
         if (!on) return;
         const auto now = std::chrono::steady_clock::now();
@@ -94,9 +94,8 @@ inline int resolve_device(int device) {
         throw Error(SCG_ERR_DEVICE, "no HIP device available: libscg has no CPU fallback");
     }
     if (device < 0) {
-        const char* env = std::getenv("SCG_DEVICE");
-        if (env && *env) {
-            device = std::atoi(env);
+        if (scg::env().device_set) {
+            device = scg::env().device;
         } else {
             HIP_CHECK(hipGetDevice(&device));
         }
@@ -335,8 +334,7 @@ struct scg_plan {
         HIP_CHECK(hipMemset(counters, 0, static_cast<size_t>(std::max<int64_t>(n_counters, 1)) * sizeof(int32_t)));
         // enough replicas that ~2^20 distinct addresses take the atomics
         replica_shift = 0;
-        int addr_log2 = 20;
-        if (const char* e = std::getenv("SCG_REPLICA_ADDR_LOG2")) addr_log2 = std::atoi(e);     // tuning aid
+        const int addr_log2 = scg::env().replica_addr_log2;
         while (n_counters > 0 && replica_shift < 12 && (n_counters << (replica_shift + 1)) <= (int64_t(1) << addr_log2)) ++replica_shift;
         if (replica_shift > 0) {
             replicas.alloc((static_cast<size_t>(n_counters) << replica_shift) * sizeof(int32_t));
@@ -495,28 +493,6 @@ struct PlanSet {
     PlanSet(std::unique_ptr<scg_plan> compiled, const std::vector<int>& devices);
     std::vector<scg_plan*> all() const;
     scg_plan* first() const { return plans[0].get(); }
-};
-
-// The switches that steer the file paths (test hooks and tuning aids), read once per file-level call.
-struct Switches {
-    bool device_scan = true;      // SCG_DEVICE_SCAN=0 keeps the host parsers
-    bool host_scan = true;        // SCG_HOST_SCAN=0 ships the raw text of plain files too
-    bool buffer_cache = true;     // SCG_BUFFER_CACHE=0 keeps no idle scan slots for the next call
-    bool device_inflate = true;   // SCG_DEVICE_INFLATE=0 inflates BGZF members on the host threads
-    // =2: a file the device inflater / gzip decoder hands back is an error instead of a quiet second try on the host
-    // (so that a test on a well-formed file cannot pass on the fall-back)
-    bool inflate_strict = false, gunzip_strict = false;      // SCG_DEVICE_INFLATE=2, SCG_DEVICE_GUNZIP=2
-    size_t window_kb = 0;         // SCG_WINDOW_KB: tiny windows force many hand-overs (0: the built-in sizes)
-    Switches() {
-        auto first = [](const char* name) { const char* e = std::getenv(name); return e ? *e : '\0'; };
-        device_scan = first("SCG_DEVICE_SCAN") != '0';
-        host_scan = first("SCG_HOST_SCAN") != '0';
-        buffer_cache = first("SCG_BUFFER_CACHE") != '0';
-        device_inflate = first("SCG_DEVICE_INFLATE") != '0';
-        inflate_strict = first("SCG_DEVICE_INFLATE") == '2';
-        gunzip_strict = first("SCG_DEVICE_GUNZIP") == '2';
-        if (const char* e = std::getenv("SCG_WINDOW_KB")) window_kb = static_cast<size_t>(std::max(0L, std::atol(e)));
-    }
 };
 
 void count_single_end_file(scg_plan* P, const char* path, scg::FastqStream& fq, int nthreads,

@@ -22,6 +22,7 @@
 #include "scg_engine.hip.h"
 #include "scg_staged.hip.h"
 #include "scg_launch.h"
+#include "scg_env.h"
 
 using namespace scgdev;
 
@@ -1114,10 +1115,7 @@ __global__ __launch_bounds__(BLOCK) void synth_kernel(scg_synth_spec S, char* __
 
 // Measurement aid ($SCG_EXTRA_LDS_KB, tools/abx.sh): unused dynamic LDS per workgroup, to see what a kernel loses when fewer
 // workgroups fit a CU.  No effect on results.
-inline size_t extra_lds() {
-    static const size_t kb = [] { const char* e = std::getenv("SCG_EXTRA_LDS_KB"); return e ? (size_t)std::atoi(e) : (size_t)0; }();
-    return kb << 10;
-}
+inline size_t extra_lds() { return scg::env().extra_lds_kb << 10; }
 inline unsigned grid_for(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 inline unsigned staged_grid(int64_t n) { return (unsigned)((n + STAGE_BLOCK - 1) / STAGE_BLOCK); }
 
@@ -1125,12 +1123,8 @@ inline unsigned staged_grid(int64_t n) { return (unsigned)((n + STAGE_BLOCK - 1)
 
 namespace scg {
 
-// Test hook: SCG_FORCE_GENERAL=1 runs the byte-wise engine alone (read at every launch so that a
-// test process can flip it).
-static bool force_general() {
-    const char* e = std::getenv("SCG_FORCE_GENERAL");
-    return e && *e && *e != '0';
-}
+// Test hook: SCG_FORCE_GENERAL=1 runs the byte-wise engine alone.
+static bool force_general() { return env().force_general; }
 
 // The staged kernels need every read to fit a tile row (<= 320 bases); batches with longer reads
 // or an unknown maximum length take the byte-wise general kernels.  One answer for the launchers
@@ -1235,11 +1229,6 @@ static double expected_chance_hits(const ScgScan& T, int max_mm, int read_len) {
     return (double)(read_len > T.len ? read_len - T.len + 1 : 1) * ways / std::pow(4.0, c);
 }
 
-static int two_tiles() {           // $SCG_DUAL_TWO_TILES=1 / 0 forces one or the other
-    static const int v = [] { const char* e = getenv("SCG_DUAL_TWO_TILES"); return e && *e ? atoi(e) : -1; }();
-    return v;
-}
-
 template<int NW, int NT> struct LaunchDual {
     template<int NC, class W>
     static void run(const ScgDualParams& P, const ScgReads& R1, const ScgReads& R2, int64_t n, const ScgCounters& counts, int32_t* flag, hipStream_t stream, bool passes) {
@@ -1261,7 +1250,7 @@ template<int NW, int NT> struct LaunchDual {
         const bool compact = compact_fits<NW>(P.scan1.compact_ok && P.scan2.compact_ok, max_len, min_t);
         if (P.diagnostics == 1) return hipErrorInvalidValue;   // the host runs include.invalid=TRUE as a plain pass followed by a masked pass of 2
         const bool wide = P.index1.wide != 0;            // barcodes of 33..64 bases on either mate (both indexes are then built wide)
-        const int forced = two_tiles();
+        const int forced = env().dual_two_tiles;          // $SCG_DUAL_TWO_TILES=1 / 0 forces one or the other
         const bool passes = P.overflow && (forced >= 0 ? forced == 0
                                            : expected_chance_hits(P.scan1, P.max_mm1, max_len) + expected_chance_hits(P.scan2, P.max_mm2, max_len) < 0.01);
         with_shape<NW>(compact, wide, [&](auto s) {

@@ -2,6 +2,7 @@
 // the kernels consume.  Replaces the constructors of kaori::ScanTemplate, SimpleBarcodeSearch,
 // SegmentedBarcodeSearch and the mismatch trie build (see scg_host.h for citations).
 #include "scg_host.h"
+#include "scg_env.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -19,7 +20,7 @@ namespace scg {
 // quarter load is the measured optimum (MI355X: config 3 -13 % at 64 slots per entry, configs 2 and 5 -4 % at 4, +1 % at
 // 8 where the tables start missing the L2).  SCG_TABLE_FACTOR overrides (tuning aid).
 static uint32_t table_factor(size_t n) {
-    if (const char* e = std::getenv("SCG_TABLE_FACTOR")) { const int v = std::atoi(e); if (v >= 2) return static_cast<uint32_t>(v); }
+    if (env().table_factor) return static_cast<uint32_t>(env().table_factor);
     if (n <= 4096) return 64;
     if (n <= 32768) return 16;
     return 4;
@@ -510,8 +511,8 @@ ScgScan build_scan(const ScgTemplate& t, int max_mm) {
     // a candidate.
     // (9 of the SCG_SEED_LEN = 10 bases a seed may have: measured -1 % on config 2, -2 % on config 3, neutral elsewhere;
     // 8 costs +11 %: a false candidate then precedes the true one in a third of the wavefronts)
-    int seed_max = SCG_SEED_LEN - 1;
-    if (const char* e = std::getenv("SCG_SEED_MAX")) { const int v = std::atoi(e); if (v >= 4 && v <= SCG_SEED_LEN) seed_max = v; }   // tuning aid
+    static_assert(Env::SEED_LEN == SCG_SEED_LEN, "scg_env.h bounds SCG_SEED_MAX by the seed length");
+    const int seed_max = env().seed_max;         // SCG_SEED_LEN - 1 unless SCG_SEED_MAX says otherwise (tuning aid)
     auto fill = [&](ScgSeeds& S, const uint8_t* pos, const uint8_t* code) {
         int want = max_mm + 1;
         if (want > SCG_MAX_SEEDS || t.nconst < want) {

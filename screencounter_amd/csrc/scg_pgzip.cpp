@@ -12,6 +12,7 @@
 #include <vector>
 #include <zlib.h>
 
+#include "scg_env.h"
 #include "scg_gzip.h"
 #include "scg_pgzip.h"
 
@@ -120,10 +121,7 @@ BufferCache& buffer_cache() {
 void ParallelGunzip::release_cached() { buffer_cache().clear(); }
 
 size_t ParallelGunzip::chunk_size_for(size_t size, int threads) {
-    if (const char* e = std::getenv("SCG_PGZIP_CHUNK_KB")) {         // test hook: tiny chunks
-        const long kb = std::atol(e);
-        if (kb >= 1) return static_cast<size_t>(kb) << 10;
-    }
+    if (env().pgzip_chunk_kb) return env().pgzip_chunk_kb << 10;    // test hook: tiny chunks
     if (threads < 2 || size < (size_t(2) << 20)) return 0;          // one libdeflate stream is as fast on such a file
     size_t c = size / (static_cast<size_t>(threads) * 8);
     c = std::max<size_t>(c, size_t(256) << 10);
@@ -162,7 +160,7 @@ struct ParallelGunzip::Impl {
     Impl(const uint8_t* d, size_t n, int threads, size_t chunk) : data(d), size(n), n_threads(std::max(1, threads)), chunk_bytes(chunk) {
         cap_symbols = std::max<size_t>(chunk_bytes * 16, size_t(1) << 16);       // a chunk that inflates more than 16-fold ends the attempt
         if (chunk_bytes >= (size_t(256) << 10) && cap_symbols <= STANDARD_SYMBOLS) cap_symbols = STANDARD_SYMBOLS;   // (interchangeable buffers; untouched pages cost nothing)
-        if (const char* e = std::getenv("SCG_PGZIP_CAP_KB")) { const long kb = std::atol(e); if (kb >= 1) cap_symbols = static_cast<size_t>(kb) << 10; }   // test hook
+        if (env().pgzip_cap_kb) cap_symbols = env().pgzip_cap_kb << 10;   // test hook
         n_chunks = std::max<size_t>(1, (size + chunk_bytes - 1) / chunk_bytes);
         chunks.resize(n_chunks);
         lookahead = static_cast<size_t>(n_threads) * 2 + 2;

@@ -16,11 +16,7 @@ bool general_only(const scg_plan* P) {
 
 // 256 MB of int32 cells: beyond that, combinations are sorted and run-length encoded.  $SCG_DENSE_CELLS moves the limit (the
 // tests run every combination case both ways).
-int64_t dense_cells() {
-    const char* e = getenv("SCG_DENSE_CELLS");
-    if (e && *e) return std::min<int64_t>(std::max<int64_t>(atoll(e), 0), int64_t(1) << 30);
-    return int64_t(1) << 26;
-}
+int64_t dense_cells() { return scg::env().dense_cells; }
 
 ScgReads make_reads(const char* d_seqs, const uint32_t* d_offsets, int32_t fixed_len, int32_t max_len) {
     ScgReads r;
@@ -30,8 +26,7 @@ ScgReads make_reads(const char* d_seqs, const uint32_t* d_offsets, int32_t fixed
     r.max_len = d_offsets ? max_len : fixed_len;
 #ifdef SCG_ABLATE
     // measurement builds only (make EXTRA=-DSCG_ABLATE OUT=...): the product library has no such switch
-    const char* ab = std::getenv("SCG_ABLATE");
-    r.ablate = ab ? std::atoi(ab) : 0;
+    r.ablate = scg::env().ablate;
 #else
     r.ablate = 0;
 #endif
@@ -402,7 +397,7 @@ void drop_pending_pairs(scg_plan* P) {
 // large enough to amortise the second kernel.  SCG_TALLY=0/1 overrides (measurement aid).
 bool use_tally(const scg_plan* P, int64_t n) {
     if (P->diagnostics) return false;      // the diagnostics kernels count several things per pair
-    if (const char* e = std::getenv("SCG_TALLY")) { if (*e) return *e != '0'; }
+    if (scg::env().tally >= 0) return scg::env().tally != 0;
     return P->n_counters >= 4096 && P->n_counters <= 4 * 80 * 1024 && n >= (int64_t(1) << 20);
 }
 
@@ -461,11 +456,9 @@ std::unique_ptr<scg_plan> compile_random(const char* constant, int strand, int m
     P->rnd.reset(new RandomTally);
     P->rnd->vstart = P->ht1.t.fstart[0];
     P->rnd->vlen = P->ht1.t.flen[0];
-    // Test hook, read here only: hashed tags keep this many hash bits (default and maximum 61), so that tests can make
+    // Test hook, used here only: hashed tags keep this many hash bits (default and maximum 61), so that tests can make
     // tags collide and exhaust the rounds.  Results never depend on it unless the rounds run out, which read-out reports.
-    if (const char* e = std::getenv("SCG_TEST_RANDOM_TAG_BITS")) {
-        if (*e) P->rnd->tag_bits = std::min(std::max(std::atoi(e), 0), 61);
-    }
+    P->rnd->tag_bits = scg::env().random_tag_bits;
     return P;
 }
 

@@ -57,14 +57,14 @@ std::vector<int> device_list(bool* explicit_list) {
         return tl_devices;
     }
     std::vector<int> out;
-    const char* env = std::getenv("SCG_DEVICES");
-    if (explicit_list) *explicit_list = env && *env && std::strcmp(env, "all") != 0;
-    if (env && *env && std::strcmp(env, "all") != 0) {
-        const char* p = env;
+    const char* list = scg::env().devices.c_str();       // (empty when unset)
+    if (explicit_list) *explicit_list = *list && std::strcmp(list, "all") != 0;
+    if (*list && std::strcmp(list, "all") != 0) {
+        const char* p = list;
         while (*p) {
             char* end = nullptr;
             const long v = std::strtol(p, &end, 10);
-            if (end == p) throw Error(SCG_ERR_DEVICE, std::string("cannot parse SCG_DEVICES='") + env + "'");
+            if (end == p) throw Error(SCG_ERR_DEVICE, std::string("cannot parse SCG_DEVICES='") + list + "'");
             if (v < 0 || v >= n) throw Error(SCG_ERR_DEVICE, "HIP device " + std::to_string(v) + " out of range (" + std::to_string(n) + " visible)");
             out.push_back(static_cast<int>(v));
             p = end;
@@ -74,7 +74,7 @@ std::vector<int> device_list(bool* explicit_list) {
         return out;
     }
     const int first = resolve_device(-1);
-    const bool only_one = std::getenv("SCG_DEVICE") && *std::getenv("SCG_DEVICE") && !(env && *env);
+    const bool only_one = scg::env().device_set && !scg::env().devices_set;
     out.push_back(first);
     if (!only_one) for (int d = 0; d < n; ++d) if (d != first) out.push_back(d);
     return out;

@@ -157,11 +157,12 @@ inline void retire_slot(std::unique_ptr<ScanSlot>& s, bool keep) {
 }
 
 // Text capacity of a window: `base` bytes (SCG_WINDOW_KB overrides it), less for small inputs.
-inline size_t window_bytes(const Switches& sw, size_t base, uint64_t hint) {
-    size_t w = sw.window_kb ? sw.window_kb << 10 : base;          // test hook: tiny windows force many hand-overs
+inline size_t window_bytes(size_t base, uint64_t hint) {
+    const size_t window_kb = scg::env().window_kb;
+    size_t w = window_kb ? window_kb << 10 : base;                // test hook: tiny windows force many hand-overs
     const uint64_t need = hint + (hint >> 4) + 4096;               // the whole input in one window when it is small
     if (need < w) w = static_cast<size_t>(need);
-    return std::max(w, sw.window_kb ? size_t(4) << 10 : scg::TextSource::min_capacity());
+    return std::max(w, window_kb ? size_t(4) << 10 : scg::TextSource::min_capacity());
 }
 constexpr size_t TEXT_WINDOW = size_t(128) << 20;
 constexpr size_t INFLATE_WINDOW = size_t(256) << 20;   // 4 000 BGZF members in flight
@@ -327,10 +328,10 @@ inline bool enable_peer_access(const std::vector<int>& devices) {
 // result over xGMI (peer access; the streams wait on each other's events).
 class WindowRing {
 public:
-    WindowRing(scg::TextSource& source, const std::vector<int>& devs, const Switches& sw, bool inflate_on_device)
-        : src(source), devices(devs), inflate(inflate_on_device), host_scan(!inflate_on_device && source.parses() && sw.host_scan), keep(sw.buffer_cache) {
+    WindowRing(scg::TextSource& source, const std::vector<int>& devs, bool inflate_on_device)
+        : src(source), devices(devs), inflate(inflate_on_device), host_scan(!inflate_on_device && source.parses() && scg::env().host_scan), keep(scg::env().buffer_cache) {
         if (inflate && devices.size() > 1 && !enable_peer_access(devices)) devices.resize(1);
-        cap_text = window_bytes(sw, inflate ? INFLATE_WINDOW : TEXT_WINDOW, source.size_hint());
+        cap_text = window_bytes(inflate ? INFLATE_WINDOW : TEXT_WINDOW, source.size_hint());
         cap_in = inflate ? inflate_window_staging(cap_text) : 0;
         for (int k = 0; k < 3; ++k) {
             for (int d : devices) {
@@ -454,17 +455,17 @@ struct MateWindows {
 class PairedPipeline {
 public:
     // device_inflate: BGZF mates may have their members inflated on the device (false: by the host threads)
-    PairedPipeline(int dev, scg::TextSource& src1, scg::TextSource& src2, const Switches& sw, bool device_inflate)
-        : device(dev), window(std::max(window_bytes(sw, TEXT_WINDOW, src1.size_hint()), window_bytes(sw, TEXT_WINDOW, src2.size_hint()))),
-          keep(sw.buffer_cache) {
+    PairedPipeline(int dev, scg::TextSource& src1, scg::TextSource& src2, bool device_inflate)
+        : device(dev), window(std::max(window_bytes(TEXT_WINDOW, src1.size_hint()), window_bytes(TEXT_WINDOW, src2.size_hint()))),
+          keep(scg::env().buffer_cache) {
         DeviceGuard g(device);
         mate[0].src = &src1; mate[1].src = &src2;
         HIP_CHECK(hipStreamCreateWithFlags(&compute, hipStreamNonBlocking));
         for (auto& m : mate) {
-            m.host_scan = m.src->parses() && sw.host_scan;
-            m.inflate = device_inflate && m.src->has_members() && sw.device_inflate;
+            m.host_scan = m.src->parses() && scg::env().host_scan;
+            m.inflate = device_inflate && m.src->has_members() && scg::env().device_inflate;
             if (m.inflate) {
-                m.cap_text = window_bytes(sw, INFLATE_WINDOW, m.src->size_hint());
+                m.cap_text = window_bytes(INFLATE_WINDOW, m.src->size_hint());
                 m.cap_in = inflate_window_staging(m.cap_text);
             }
             for (int k = 0; k < 2; ++k) {
@@ -581,8 +582,8 @@ private:
 // -------------------------------------------------------------------------------------------------
 class PairedRounds {
 public:
-    PairedRounds(const std::vector<int>& devs, scg::TextSource& src1, scg::TextSource& src2, const Switches& sw)
-        : devices(devs), window(std::max(window_bytes(sw, TEXT_WINDOW, src1.size_hint()), window_bytes(sw, TEXT_WINDOW, src2.size_hint()))) {
+    PairedRounds(const std::vector<int>& devs, scg::TextSource& src1, scg::TextSource& src2)
+        : devices(devs), window(std::max(window_bytes(TEXT_WINDOW, src1.size_hint()), window_bytes(TEXT_WINDOW, src2.size_hint()))) {
         mate[0].src = &src1; mate[1].src = &src2;
         cap_lines = window / 16 + 1024;
         cap_records = cap_lines / 4 + 1;

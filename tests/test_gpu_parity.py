@@ -106,6 +106,31 @@ def test_dual_random(sc, oracle, gpu, seed, hazard_free, wide):
         assert np.array_equal(got[0], exp[0]), case
 
 
+def test_dual_two_tiles_switch_is_read_per_call(sc, oracle, gpu, monkeypatch):
+    """SCG_DUAL_TWO_TILES picks the pair search per call (it was frozen at its first use in the process): 257 pairs,
+    one past a 256-read tile, on one non-diagnostics plan with the passes search forced, the two-tile search forced
+    and the library's own choice, the plan reset in between.  Every count equals the oracle's."""
+    case = gen.random_dual_case(random.Random(3100), sizes=(257,), max_mm=2)
+    assert len(case["reads1"]) == len(case["reads2"]) == 257
+    exp = oracle.count_dual(case["reads1"], case["reads2"], case["template1"], case["reverse1"], case["mismatches1"], case["pool1"],
+                            case["template2"], case["reverse2"], case["mismatches2"], case["pool2"], case["randomized"], case["use_first"])
+    s1, o1 = sc.upload_reads(case["reads1"], gpu)
+    s2, o2 = sc.upload_reads(case["reads2"], gpu)
+    with sc.Plan.dual(case["template1"], case["reverse1"], case["mismatches1"], case["pool1"],
+                      case["template2"], case["reverse2"], case["mismatches2"], case["pool2"],
+                      case["randomized"], case["use_first"]) as plan:
+        for forced in ("0", "1", None):
+            if forced is None:
+                monkeypatch.delenv("SCG_DUAL_TWO_TILES", raising=False)
+            else:
+                monkeypatch.setenv("SCG_DUAL_TWO_TILES", forced)
+            plan.reset()
+            plan.count_paired(s1, s2, o1, o2)
+            got = plan.read()
+            assert got[1] == exp[1] == 257, forced
+            assert np.array_equal(got[0], exp[0]), forced
+
+
 @pytest.mark.parametrize("seed", range(4))
 def test_match_random(sc, oracle, gpu, seed):
     from oracle.pyoracle import OracleError
