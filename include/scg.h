@@ -221,7 +221,8 @@ int scg_count_single_barcodes_files(const char* const* paths, int32_t n_files, c
 
 /* indices_out / freq_out / k_out: n_files entries each, caller-allocated arrays; entry f receives file f's malloc'd
  * 2 x K_f matrix, K_f frequencies and K_f exactly as scg_count_combo_barcodes_single returns them (release every
- * entry with scg_free).  The caller merges them as combineComboCounts does (R/combineComboCounts.R:31-57). */
+ * entry with scg_free).  The caller merges them as combineComboCounts does (R/combineComboCounts.R:31-57), or calls
+ * scg_count_combo_barcodes_single_matrix below, which returns the merged matrix. */
 int scg_count_combo_barcodes_single_files(const char* const* paths, int32_t n_files, const char* constant, int strand,
                                           const char* const* pool0, int32_t n_pool0,
                                           const char* const* pool1, int32_t n_pool1,
@@ -312,6 +313,63 @@ int scg_count_random_barcodes_files(const char* const* paths, int32_t n_files,
                                     char** sequences_out, int64_t* k_out, int32_t* length_out,
                                     int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out,
                                     int32_t* totals_out, char* err, size_t errcap);
+
+/* ---------------------------------------------------------------------------------------------
+ * Combination counts of many files as one matrix: what matrixOfComboBarcodes and matrixOfPairedComboBarcodes return
+ * after combineComboCounts (R/combineComboCounts.R:31-57), and what the invalid pairs of the two include.invalid=TRUE
+ * functions become there.  The three entries below hand out one shape, that of scg_count_random_barcodes_files:
+ *   *indices_out   malloc'd 2 x K column-major matrix of 0-based indices, the union of the files' combinations sorted by
+ *                  (first, second) -- the layout of the one-file entries;
+ *   *k_out         K;
+ *   *col_ptr_out   n_files + 1 entries: column f is entries (*col_ptr_out)[f] .. (*col_ptr_out)[f + 1] - 1 of
+ *   *rows_out      (0-based rows of the union, ascending within a column) and
+ *   *freq_out      (the counts).
+ * Release the four arrays with scg_free; after a failed call they are null, K is 0 and there is nothing to free.  A null
+ * pointer or n_files < 0 is SCG_ERR_INVALID; n_files == 0 succeeds with K = 0 and four arrays to release.
+ * The union is computed on the first device of the call's list (scg_set_devices / $SCG_DEVICES): the files' lists are
+ * uploaded once, back to back, as 64-bit keys (first << 32 | second); a radix sort and run-length encode give the distinct
+ * keys, and every entry finds its row by a lower bound over them -- asynchronous on one stream, one wait.  Limits, reported
+ * and never truncated: more than 4294967295 combinations over all files is SCG_ERR_UNSUPPORTED; more than INT32_MAX distinct
+ * ones is SCG_ERR_INVALID ("number of distinct barcode combinations exceeds the 32-bit range of the row indices"); device
+ * memory that cannot be had is SCG_ERR_DEVICE with the sizes asked for (about 40 bytes per combination).
+ * ------------------------------------------------------------------------------------------- */
+
+/* combineComboCounts itself, for per-file lists the caller already holds -- indices[f] / freq[f] / k[f] as the one-file and
+ * *_files entries return them (the invalid pairs of the diagnostics entries included), in any order.  An entry with count
+ * 0 keeps its row (out.counts[cbind(id, origin)] <- counts).  A combination that appears twice within one list fails with
+ * the reference's "barcode combinations should be unique within each DataFrame in '...'" (SCG_ERR_INVALID); a negative
+ * index or a negative k[f] is SCG_ERR_INVALID.  Every list is sorted by key on the device, with its counts. */
+int scg_combine_combinations(const int32_t* const* indices, const int32_t* const* freq, const int64_t* k, int32_t n_files,
+                             int32_t** indices_out, int64_t* k_out, int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out,
+                             char* err, size_t errcap);
+
+/* matrixOfComboBarcodes (R/countComboBarcodes.R:149-164) in one call: the arguments of scg_count_combo_barcodes_single_files,
+ * every file counted as there (template and pools compiled once, a device takes the next file when it is free, the error
+ * of the lowest-numbered failing file -- the one-file entry's message -- is reported), and totals_out[f] file f's reads.
+ * The first file's reader comes first, then the argument errors of scg_count_combo_barcodes_single, both before any device
+ * work.  A file's dense histogram (n_pool0 x n_pool1 <= 2^26 cells) is compacted on the device that counted it: tiles of
+ * 4096 cells are counted, the counts scanned and the non-zero cells scattered in order, so that K_f (key, count) pairs
+ * cross the link and no cell is looked at by the host; a plan in sparse mode hands over its sorted list.  Column f is what
+ * scg_count_combo_barcodes_single returns for paths[f] alone. */
+int scg_count_combo_barcodes_single_matrix(const char* const* paths, int32_t n_files, const char* constant, int strand,
+                                           const char* const* pool0, int32_t n_pool0,
+                                           const char* const* pool1, int32_t n_pool1,
+                                           int mismatches, int use_first, int nthreads,
+                                           int32_t** indices_out, int64_t* k_out, int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out,
+                                           int32_t* totals_out, char* err, size_t errcap);
+
+/* matrixOfPairedComboBarcodes (R/countPairedComboBarcodes.R) in one call: the arguments and the contract of
+ * scg_count_combo_barcodes_paired_files (argument errors before any file is opened and any device is touched); totals_out,
+ * barcode1_only_out, barcode2_only_out: n_files entries each.  A file's list is read as scg_count_combo_barcodes_paired
+ * reads it (sequence uids merged to pool indices on the host); only the union is done on the device. */
+int scg_count_combo_barcodes_paired_matrix(const char* const* paths1, const char* constant1, int reverse1, int mismatches1,
+                                           const char* const* pool1, int32_t n_pool1,
+                                           const char* const* paths2, const char* constant2, int reverse2, int mismatches2,
+                                           const char* const* pool2, int32_t n_pool2, int32_t n_files,
+                                           int randomized, int use_first, int nthreads,
+                                           int32_t** indices_out, int64_t* k_out, int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out,
+                                           int32_t* totals_out, int32_t* barcode1_only_out, int32_t* barcode2_only_out,
+                                           char* err, size_t errcap);
 
 /* matchBarcodes.  Replaces src/match_barcodes.cpp:6-37.  index_out[i] is the 0-based index of the
  * unique best choice within `substitutions` mismatches or -1 (R: NA); mismatches_out likewise. */
@@ -516,6 +574,13 @@ int scg_plan_read_diagnostics(scg_plan* plan, int32_t* counts_out, int32_t** inv
 int scg_combo_compact(const int32_t* cells, int32_t n_pool0, int32_t n_pool1,
                       int32_t** indices_out, int32_t** freq_out, int64_t* k_out,
                       char* err, size_t errcap);
+
+/* The same contract on the device (host cells in, host lists out): the cells are uploaded to the calling thread's current
+ * device, compacted there by the kernels the matrix entries use for a counted file (csrc/scg_combine.hip) and only the K
+ * pairs are copied back.  SCG_ERR_DEVICE without a device. */
+int scg_combo_compact_device(const int32_t* cells, int32_t n_pool0, int32_t n_pool1,
+                             int32_t** indices_out, int32_t** freq_out, int64_t* k_out,
+                             char* err, size_t errcap);
 
 /* Kernel timing for the roofline figure: while profiling is on, every counting-kernel launch
  * issued through the plan is bracketed by HIP events recorded on the launch stream.

@@ -5,7 +5,7 @@ screencounter_amd/csrc``).  There is no fallback of any kind: if the library is 
 import fails, and if no HIP device is present every counting call returns SCG_ERR_DEVICE.
 
 Besides the signatures: the marshalling steps that api.py and engine.py share, each written once -- strings and pools in
-(cstr_array, pool, cstr_matrix), combinations out (combo_outputs, per_file_combo_outputs) and sequence blobs out
+(cstr_array, pool, cstr_matrix), combinations out (combo_outputs, per_file_combo_outputs, combo_matrix_outputs) and sequence blobs out
 (decode_sequences).
 """
 from __future__ import annotations
@@ -57,7 +57,9 @@ ERR = [STR, C.c_size_t]                           # char* err, size_t errcap
 POOL = [c_str_p, I32]                             # const char* const* pool, int32_t n_pool
 POOLS = [C.POINTER(c_str_p), i32_p, I32]          # const char* const* const* pools, const int32_t* n_pools, int32_t n_regions
 COMBOS = [C.POINTER(i32_p), C.POINTER(i32_p), i64_p]     # int32_t** indices_out, int32_t** freq_out, int64_t* k_out (one entry, or one per file)
-READS = [PTR, PTR, I32]                           # const char* d_seqs, const uint32_t* d_offsets, int32_t fixed_len
+# int32_t** indices_out, int64_t* k_out, int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out (the combination matrix)
+MATRIX = [C.POINTER(i32_p), i64_p, C.POINTER(i64_p), C.POINTER(i32_p), C.POINTER(i32_p)]
+READS = [PTR, PTR, I32]                          # const char* d_seqs, const uint32_t* d_offsets, int32_t fixed_len
 PLAN_OUT = C.POINTER(PTR)                         # scg_plan** plan_out
 
 # name -> (restype, argtypes); must list every symbol declared in include/scg.h
@@ -85,6 +87,11 @@ SIGNATURES = {
                                                     INT, INT, INT, *COMBOS, i32_p, i32_p, i32_p, *ERR]),
     "scg_count_random_barcodes_files": (INT, [c_str_p, I32, STR, INT, INT, INT, INT,
                                               C.POINTER(PTR), i64_p, i32_p, C.POINTER(i64_p), C.POINTER(i32_p), C.POINTER(i32_p), i32_p, *ERR]),
+    "scg_combine_combinations": (INT, [C.POINTER(i32_p), C.POINTER(i32_p), i64_p, I32, *MATRIX, *ERR]),
+    "scg_count_combo_barcodes_single_matrix": (INT, [c_str_p, I32, STR, INT, *POOL, *POOL, INT, INT, INT, *MATRIX, i32_p, *ERR]),
+    "scg_count_combo_barcodes_paired_matrix": (INT, [c_str_p, STR, INT, INT, *POOL, c_str_p, STR, INT, INT, *POOL, I32,
+                                                     INT, INT, INT, *MATRIX, i32_p, i32_p, i32_p, *ERR]),
+    "scg_combo_compact_device": (INT, [i32_p, I32, I32, *COMBOS, *ERR]),
     "scg_fastq_text_windows": (INT, [STR, I64, INT, C.POINTER(PTR), i64_p, C.POINTER(PTR), i64_p, STR, *ERR]),
     "scg_fastq_scan_windows": (INT, [STR, I64, INT, C.POINTER(PTR), C.POINTER(PTR), i64_p, i64_p, *ERR]),
     "scg_bgzf_member_batches": (INT, [STR, I64, I64, INT, C.POINTER(PTR), i64_p, C.POINTER(PTR), i64_p, i64_p, *ERR]),
@@ -240,6 +247,31 @@ def combo_outputs(L):
     entry: take() -> (indices int32[2, K], freq int32[K])."""
     with per_file_combo_outputs(L, 1) as (outputs, take):
         yield outputs, lambda: take()[0]
+
+
+@contextlib.contextmanager
+def combo_matrix_outputs(L, n: int):
+    """The five outputs of an entry that returns the combination matrix of n files (int32_t** indices_out, int64_t* k_out,
+    int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out).  `with ... as (outputs, take)`: pass `*outputs` to the
+    call; after it, take() -> (indices int32[2, K], matrix int32[K, n] dense, as R's out.counts), fresh arrays that own their
+    memory.  Leaving the block frees the four arrays, whatever happened inside."""
+    idx, colptr, rows, freq, k = i32_p(), i64_p(), i32_p(), i32_p(), C.c_int64(0)
+
+    def take():
+        K = int(k.value)
+        col = np.ctypeslib.as_array(colptr, shape=(n + 1,)).copy()
+        nnz = int(col[n])
+        indices = np.ctypeslib.as_array(idx, shape=(K, 2)).T.copy() if K else np.zeros((2, 0), dtype=np.int32)
+        matrix = np.zeros((K, n), dtype=np.int32)
+        if nnz:
+            r = np.ctypeslib.as_array(rows, shape=(nnz,))
+            matrix[r, np.repeat(np.arange(n), np.diff(col))] = np.ctypeslib.as_array(freq, shape=(nnz,))
+        return indices, matrix
+    try:
+        yield (C.byref(idx), C.byref(k), C.byref(colptr), C.byref(rows), C.byref(freq)), take
+    finally:
+        for p in (idx, colptr, rows, freq):
+            L.scg_free(p)
 
 
 def decode_sequences(ptr, K: int, W: int):

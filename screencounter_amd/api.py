@@ -341,6 +341,71 @@ def count_random_barcodes_files(paths: Sequence[str], constant: str, strand: int
 
 
 # =============================================================================================
+# Combination counts of many files as one matrix (combineComboCounts on the device)
+# =============================================================================================
+def combine_combinations(lists: Sequence, devices=None):
+    """scg_combine_combinations: combineComboCounts (R/combineComboCounts.R:31-57) for per-file lists of
+    (indices int32[2, K_f], freq int32[K_f]) in any order -> (indices int32[2, K]: the union sorted by (first, second),
+    matrix int32[K, len(lists)] dense)."""
+    L, err = _lib.load(), errbuf()
+    n = len(lists)
+    idx = [np.ascontiguousarray(np.asarray(i, dtype=np.int32).reshape(2, -1).T) for i, _ in lists]     # K_f x 2: the C layout
+    freq = [np.ascontiguousarray(f, dtype=np.int32).reshape(-1) for _, f in lists]
+    for i, f in zip(idx, freq):
+        if len(i) != len(f):
+            raise ValueError("indices and freq differ in length")
+    idx_p, freq_p, ks = (i32_p * max(n, 1))(), (i32_p * max(n, 1))(), (C.c_int64 * max(n, 1))()
+    for f in range(n):
+        idx_p[f], freq_p[f], ks[f] = idx[f].ctypes.data_as(i32_p), freq[f].ctypes.data_as(i32_p), len(freq[f])
+    with _devices_env(devices), _lib.combo_matrix_outputs(L, n) as (matrix, take):
+        check(L.scg_combine_combinations(idx_p, freq_p, ks, n, *matrix, err, ERRCAP), err)
+        return take()
+
+
+def count_combo_barcodes_single_matrix(paths: Sequence[str], constant: str, strand: int, pool: Sequence[Sequence[str]], mismatches: int,
+                                       use_first: bool, nthreads: int = 1, devices=None):
+    """scg_count_combo_barcodes_single_matrix: matrixOfComboBarcodes in one native call, the files' combinations merged on
+    the device -> (indices int32[2, K]: the union sorted by (first, second), matrix int32[K, n_files] dense as
+    combineComboCounts builds it, totals int32[n_files])."""
+    if len(pool) != 2:
+        raise ScgError(_lib.SCG_ERR_INVALID, TWO_REGIONS)
+    L, err = _lib.load(), errbuf()
+    with _files_call(devices, paths) as (n, (farr,), (totals,)), _lib.combo_matrix_outputs(L, n) as (matrix, take):
+        check(L.scg_count_combo_barcodes_single_matrix(farr, n, constant.encode(), int(strand), *_lib.pool(pool[0]), *_lib.pool(pool[1]),
+                                                       int(mismatches), int(bool(use_first)), int(nthreads), *matrix, totals, err, ERRCAP), err)
+        return (*take(), np.array(totals[:n], dtype=np.int32))
+
+
+def count_combo_barcodes_paired_matrix(paths1: Sequence[str], constant1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],
+                                       paths2: Sequence[str], constant2: str, reverse2: bool, mismatches2: int, pool2: Sequence[str],
+                                       randomized: bool, use_first: bool, nthreads: int = 1, devices=None):
+    """scg_count_combo_barcodes_paired_matrix: matrixOfPairedComboBarcodes in one native call -> (indices int32[2, K],
+    matrix int32[K, n_files] dense, totals int32[n_files], barcode1_only int32[n_files], barcode2_only int32[n_files])."""
+    if len(paths1) != len(paths2):
+        raise ValueError("paths1 and paths2 differ in length")
+    L, err = _lib.load(), errbuf()
+    with _files_call(devices, paths1, paths2, scalars=3) as (n, (f1, f2), (totals, b1, b2)), _lib.combo_matrix_outputs(L, n) as (matrix, take):
+        check(L.scg_count_combo_barcodes_paired_matrix(f1, constant1.encode(), int(bool(reverse1)), int(mismatches1), *_lib.pool(pool1),
+                                                       f2, constant2.encode(), int(bool(reverse2)), int(mismatches2), *_lib.pool(pool2), n,
+                                                       int(bool(randomized)), int(bool(use_first)), int(nthreads),
+                                                       *matrix, totals, b1, b2, err, ERRCAP), err)
+        return (*take(), *(np.array(x[:n], dtype=np.int32) for x in (totals, b1, b2)))
+
+
+def combo_compact_device(cells: np.ndarray, n0: int, n1: int):
+    """scg_combo_compact_device: engine.combo_compact with the compaction done by the device kernels of the matrix entries
+    -> (indices int32[2, K], freq int32[K])."""
+    L, err = _lib.load(), errbuf()
+    cells = np.ascontiguousarray(cells, dtype=np.int32)
+    if cells.size < n0 * n1:
+        raise ValueError("cells too short")
+    src = cells if cells.size else np.zeros(1, dtype=np.int32)
+    with combo_outputs(L) as (combos, take):
+        check(L.scg_combo_compact_device(src.ctypes.data_as(i32_p), int(n0), int(n1), *combos, err, ERRCAP), err)
+        return take()
+
+
+# =============================================================================================
 # Per-read assignment, match_barcodes, parse_fastq
 # =============================================================================================
 def assign_single_barcodes(path: str, template: str, strand: int, pool: Sequence[str], mismatches: int = 0, use_first: bool = True,

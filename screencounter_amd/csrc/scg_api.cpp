@@ -786,6 +786,131 @@ int scg_count_random_barcodes_files(const char* const* paths, int32_t n_files, c
     });
 }
 
+// ---- combination counts of many files as one matrix (matrixOfComboBarcodes, matrixOfPairedComboBarcodes) ----------------
+// The three entries below hand out what combineComboCounts builds (R/combineComboCounts.R:31-57) in the shape of
+// scg_count_random_barcodes_files: the union of the files' combinations as rows, one compressed column per file.  The
+// files are counted as in the *_files entries; a file leaves its device as sorted (key, count) pairs -- a dense histogram
+// is compacted where it was counted (scg_combine.hip) -- and the union runs on the first device when all files are done.
+
+int scg_combine_combinations(const int32_t* const* indices, const int32_t* const* freq, const int64_t* k, int32_t n_files,
+                             int32_t** indices_out, int64_t* k_out, int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out,
+                             char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (!indices_out || !k_out || !col_ptr_out || !rows_out || !freq_out) throw Error(SCG_ERR_INVALID, "null argument");
+        *indices_out = nullptr; *col_ptr_out = nullptr; *rows_out = nullptr; *freq_out = nullptr; *k_out = 0;
+        if (n_files < 0 || (n_files > 0 && (!indices || !freq || !k))) throw Error(SCG_ERR_INVALID, "null argument");
+        std::vector<ComboList> lists(static_cast<size_t>(n_files));
+        for (int32_t f = 0; f < n_files; ++f) {
+            if (k[f] < 0) throw Error(SCG_ERR_INVALID, "negative number of combinations");
+            if (k[f] > 0 && (!indices[f] || !freq[f])) throw Error(SCG_ERR_INVALID, "null argument");
+            combo_list_of_outputs(indices[f], freq[f], k[f], lists[static_cast<size_t>(f)]);
+        }
+        if (n_files == 0) {                                            // an empty matrix, with arrays to release like any other
+            empty_combo_matrix(0, indices_out, k_out, col_ptr_out, rows_out, freq_out);
+            return;
+        }
+        combine_lists(lists, false, device_list()[0], indices_out, k_out, col_ptr_out, rows_out, freq_out);
+    });
+}
+
+int scg_count_combo_barcodes_single_matrix(const char* const* paths, int32_t n_files, const char* constant, int strand,
+                                           const char* const* pool0, int32_t n_pool0, const char* const* pool1, int32_t n_pool1,
+                                           int mismatches, int use_first, int nthreads,
+                                           int32_t** indices_out, int64_t* k_out, int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out,
+                                           int32_t* totals_out, char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (!indices_out || !k_out || !col_ptr_out || !rows_out || !freq_out) throw Error(SCG_ERR_INVALID, "null argument");
+        *indices_out = nullptr; *col_ptr_out = nullptr; *rows_out = nullptr; *freq_out = nullptr; *k_out = 0;
+        if (n_files < 0 || (n_files > 0 && (!paths || !totals_out))) throw Error(SCG_ERR_INVALID, "null argument");
+        std::vector<ComboList> lists(static_cast<size_t>(n_files));
+        std::vector<int32_t> totals(static_cast<size_t>(n_files), 0);
+        const std::unique_ptr<PlanSet> set = count_files(FileLists{paths, nullptr, n_files}, nthreads, Order::FILE0_THEN_ARGUMENTS, [&] {
+            return compile_combo(constant, strand, pool0, n_pool0, pool1, n_pool1, mismatches, use_first);
+        }, [&](scg_plan* P, int32_t f) {
+            totals[static_cast<size_t>(f)] = narrow_total(P->total);
+            combo_list_of_plan(P, lists[static_cast<size_t>(f)]);
+        });
+        if (n_files == 0) {
+            empty_combo_matrix(0, indices_out, k_out, col_ptr_out, rows_out, freq_out);
+            return;
+        }
+        combine_lists(lists, true, set->first()->device, indices_out, k_out, col_ptr_out, rows_out, freq_out);
+        std::copy(totals.begin(), totals.end(), totals_out);
+    });
+}
+
+int scg_count_combo_barcodes_paired_matrix(const char* const* paths1, const char* constant1, int reverse1, int mismatches1,
+                                           const char* const* pool1, int32_t n_pool1,
+                                           const char* const* paths2, const char* constant2, int reverse2, int mismatches2,
+                                           const char* const* pool2, int32_t n_pool2, int32_t n_files,
+                                           int randomized, int use_first, int nthreads,
+                                           int32_t** indices_out, int64_t* k_out, int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out,
+                                           int32_t* totals_out, int32_t* barcode1_only_out, int32_t* barcode2_only_out,
+                                           char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (!indices_out || !k_out || !col_ptr_out || !rows_out || !freq_out) throw Error(SCG_ERR_INVALID, "null argument");
+        *indices_out = nullptr; *col_ptr_out = nullptr; *rows_out = nullptr; *freq_out = nullptr; *k_out = 0;
+        if (n_files < 0 || (n_files > 0 && (!paths1 || !paths2 || !totals_out || !barcode1_only_out || !barcode2_only_out))) {
+            throw Error(SCG_ERR_INVALID, "null argument");
+        }
+        const size_t n = static_cast<size_t>(n_files);
+        std::vector<ComboList> lists(n);
+        std::vector<int32_t> totals(n, 0), b1(n, 0), b2(n, 0);
+        const std::unique_ptr<PlanSet> set = count_files(FileLists{paths1, paths2, n_files}, nthreads, Order::ARGUMENTS_FIRST, [&] {
+            return compile_paired_combo(constant1, reverse1, mismatches1, pool1, n_pool1, constant2, reverse2, mismatches2, pool2, n_pool2,
+                                        randomized, use_first);
+        }, [&](scg_plan* P, int32_t f) {
+            // the file's list by the read-out of the paired entries (sequence uids to pool indices on the host)
+            int32_t* idx = nullptr;
+            int32_t* fr = nullptr;
+            int64_t kf = 0;
+            result_diagnostics(std::vector<scg_plan*>(1, P), nullptr, &idx, &fr, &kf, &totals[static_cast<size_t>(f)], &b1[static_cast<size_t>(f)],
+                               &b2[static_cast<size_t>(f)]);
+            const std::unique_ptr<int32_t, void (*)(void*)> keep_idx(idx, std::free), keep_fr(fr, std::free);
+            combo_list_of_outputs(idx, fr, kf, lists[static_cast<size_t>(f)]);
+        });
+        if (n_files == 0) {
+            empty_combo_matrix(0, indices_out, k_out, col_ptr_out, rows_out, freq_out);
+            return;
+        }
+        combine_lists(lists, true, set->first()->device, indices_out, k_out, col_ptr_out, rows_out, freq_out);
+        std::copy(totals.begin(), totals.end(), totals_out);
+        std::copy(b1.begin(), b1.end(), barcode1_only_out);
+        std::copy(b2.begin(), b2.end(), barcode2_only_out);
+    });
+}
+
+int scg_combo_compact_device(const int32_t* cells, int32_t n_pool0, int32_t n_pool1,
+                             int32_t** indices_out, int32_t** freq_out, int64_t* k_out, char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (!cells || !indices_out || !freq_out || !k_out) throw Error(SCG_ERR_INVALID, "null argument");
+        *indices_out = nullptr; *freq_out = nullptr; *k_out = 0;
+        const int device = resolve_device(-1);
+        DeviceGuard g(device);
+        const uint64_t n_cells = n_pool0 > 0 && n_pool1 > 0 ? static_cast<uint64_t>(n_pool0) * static_cast<uint64_t>(n_pool1) : 0;
+        ComboList list;
+        if (n_cells) {
+            DevBuf d_cells;
+            try {
+                d_cells.alloc(n_cells * sizeof(int32_t));
+            } catch (const Error& e) {
+                throw Error(SCG_ERR_DEVICE, "cannot allocate " + std::to_string(n_cells) + " cells on the device: " + e.what());
+            }
+            HIP_CHECK(hipMemcpy(d_cells.p, cells, n_cells * sizeof(int32_t), hipMemcpyHostToDevice));
+            compact_cells_on_device(d_cells.as<int32_t>(), n_pool0, n_pool1, list);
+        }
+        const size_t K = list.keys.size();
+        OutPair<int32_t, int32_t> out(2 * K + 1, K + 1);
+        for (size_t j = 0; j < K; ++j) {
+            out.a[2 * j] = static_cast<int32_t>(list.keys[j] >> 32);
+            out.a[2 * j + 1] = static_cast<int32_t>(list.keys[j] & 0xFFFFFFFFu);
+            out.b[j] = list.counts[j];
+        }
+        out.release(indices_out, freq_out);
+        *k_out = static_cast<int64_t>(K);
+    });
+}
+
 int scg_plan_read_diagnostics(scg_plan* plan, int32_t* counts_out, int32_t** invalid_indices_out, int32_t** invalid_freq_out,
                               int64_t* k_out, int64_t* total_out, int32_t* barcode1_only_out, int32_t* barcode2_only_out,
                               void* stream, char* err, size_t errcap) {

@@ -545,6 +545,29 @@ void result_combinations(const std::vector<scg_plan*>& plans, int32_t** idx_out,
 // no counts_out; b1_out / b2_out may be null)
 void result_diagnostics(const std::vector<scg_plan*>& plans, int32_t* counts_out, int32_t** idx_out, int32_t** freq_out, int64_t* k_out,
                         int32_t* total_out, int32_t* b1_out, int32_t* b2_out);
+// Combination counts of many files as one matrix (combineComboCounts, R/combineComboCounts.R:31-57; scg_combine.hip).
+// One file's combinations: keys (first << 32 | second) with their counts.
+struct ComboList {
+    std::vector<uint64_t> keys;
+    std::vector<int32_t> counts;
+};
+// The non-zero cells of a dense n0 x n1 histogram in the current device's memory (16-byte aligned), compacted there: only
+// the pairs come back, ascending by key.  Synchronises its own stream.
+void compact_cells_on_device(const int32_t* d_cells, int32_t n0, int32_t n1, ComboList& out);
+// A counted combination plan as such a list: the flag check and the folds of read_counters first, then the dense cells
+// compacted on the plan's device, or the sorted list of a plan in sparse mode.
+void combo_list_of_plan(scg_plan* P, ComboList& out);
+// A 2 x K matrix of indices with its K counts as such a list.
+void combo_list_of_outputs(const int32_t* idx, const int32_t* freq, int64_t k, ComboList& out);
+// The union on `device`: the distinct keys of all lists ascending as a malloc'd 2 x K matrix, and every list as a column
+// of (row, count) entries with ascending rows, in compressed-column form (scg_combine_combinations).  sorted_unique: every
+// list is ascending without repeats (the counting entries' own lists); otherwise the lists are sorted on the device and a
+// repeat within one list is the reference's error.
+void combine_lists(const std::vector<ComboList>& lists, bool sorted_unique, int device, int32_t** indices_out, int64_t* k_out,
+                   int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out);
+// The same matrix without entries: four arrays to release, K = 0, n_files + 1 zeros in col_ptr.
+void empty_combo_matrix(int32_t n_files, int32_t** indices_out, int64_t* k_out, int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out);
+
 // The per-file malloc'd outputs of a many-files entry (caller-allocated arrays of n_files entries): all-NULL before `body`
 // runs, and again -- everything released -- when it throws, so that the caller never has to guess what to free.
 void with_per_file_outputs(int32_t** idx_out, int32_t** freq_out, int64_t* k_out, int32_t n_files, const std::function<void()>& body);

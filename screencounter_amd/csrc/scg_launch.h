@@ -34,6 +34,32 @@ hipError_t launch_tally(const int32_t* unit_index, int64_t n, int32_t* counters,
 size_t sort_rle_scratch_bytes(size_t n);
 hipError_t launch_sort_rle(const uint64_t* d_keys, uint64_t* d_sorted, size_t n, uint64_t* d_unique, uint32_t* d_counts, uint32_t* d_runs,
                            void* d_scratch, size_t scratch_bytes, hipStream_t stream);
+// ---- combination counts of many files as one matrix (scg_combine.hip) ----
+// Dense cells -> (key, count) pairs of the non-zero cells, in cell order = ascending key order (key = first << 32 | second,
+// cell = first * n1 + second).  One tile of SCG_COMPACT_TILE_CELLS cells per 256-lane workgroup, two passes with a scan of
+// the tiles' counts between them; no atomics, no workgroup waits for another.
+#define SCG_COMPACT_TILE_CELLS 4096
+inline uint64_t compact_tiles(uint64_t n_cells) { return (n_cells + SCG_COMPACT_TILE_CELLS - 1) / SCG_COMPACT_TILE_CELLS; }
+size_t compact_scan_scratch_bytes(uint64_t n_cells);
+// Pass 1 and the scan: d_tile_offsets[t] = non-zero cells in the tiles before t, for t = 0 .. compact_tiles(n_cells); the
+// last entry is their number K.  d_tile_offsets and d_tile_counts: compact_tiles(n_cells) + 1 entries each.  cells must be
+// 16-byte aligned.
+hipError_t launch_compact_count(const int32_t* cells, uint64_t n_cells, unsigned long long* d_tile_counts, unsigned long long* d_tile_offsets,
+                                void* d_scratch, size_t scratch_bytes, hipStream_t stream);
+// Pass 2 over the same, unchanged cells: keys_out / counts_out get the K pairs.
+hipError_t launch_compact_scatter(const int32_t* cells, uint64_t n_cells, uint32_t n1, const unsigned long long* d_tile_offsets,
+                                  uint64_t* keys_out, int32_t* counts_out, hipStream_t stream);
+// Rows of a union: rows_out[i] = the place of keys[i] in the ascending distinct keys d_unique[0 .. *d_n_unique), for n
+// entries; *d_flag is set when a key is not among them (never expected).
+hipError_t launch_union_rows(const uint64_t* keys, uint64_t n, const uint64_t* d_unique, const uint32_t* d_n_unique, int32_t* rows_out,
+                             int32_t* d_flag, hipStream_t stream);
+// One file's list, sorted by key: keys and their counts (n entries, 64 key bits); scratch of sort_pairs_scratch_bytes(n).
+size_t sort_pairs_scratch_bytes(size_t n);
+hipError_t launch_sort_pairs(const uint64_t* keys_in, uint64_t* keys_out, const int32_t* vals_in, int32_t* vals_out, size_t n,
+                             void* d_scratch, size_t scratch_bytes, hipStream_t stream);
+// *d_flag is set when two neighbours of the sorted list keys[0 .. n) are equal.
+hipError_t launch_flag_equal_neighbours(const uint64_t* keys, uint64_t n, int32_t* d_flag, hipStream_t stream);
+
 // ---- random-barcode plans: the tally in HBM (scg_random.hip) ----
 // Open-addressing table of capacity mask + 1 (a power of two).  Slot s: tags[s] (0 = empty), counts[s], and for hashed
 // tags the key bytes at arena[s * vlen].  Tag layout: bit 63 clear, bit 62 set, 2 bits per base MSB first below = a

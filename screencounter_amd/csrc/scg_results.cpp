@@ -1,6 +1,7 @@
 // scg_results.cpp -- what a file-level call has around its pipelines: the devices it may use, the plans on them (PlanSet),
 // the scheduling of many files over them, and the shaping of counters into the reference's outputs: one reader per kind
-// of result (result_counts, result_combinations, result_diagnostics), shared by the plan, one-file and many-files entries.
+// of result (result_counts, result_combinations, result_diagnostics), shared by the plan, one-file and many-files entries;
+// and the matrices of many files: random barcodes (result_random_matrix) and combinations (combine_lists, on the device).
 #include "scg_internal.hpp"
 #include "scg_gzip.h"
 
@@ -422,6 +423,187 @@ void result_random_matrix(const PlanSet& set, const std::vector<int>& plan_of, c
     head.release(sequences_out, col_ptr_out);
     body.release(rows_out, freq_out);
     *k_out = static_cast<int64_t>(K); *length_out = vlen;
+}
+
+// ---- combination counts of many files as one matrix (combineComboCounts, R/combineComboCounts.R:31-57) -------------------
+namespace {
+
+// A stream of its own for one compaction or one union: the workers of a many-files call share devices.
+struct OwnStream {
+    hipStream_t s = nullptr;
+    OwnStream() { HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+    OwnStream(const OwnStream&) = delete;
+    OwnStream& operator=(const OwnStream&) = delete;
+    ~OwnStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+};
+
+// Device buffers of `what`, all or SCG_ERR_DEVICE with the sizes asked for.
+void alloc_all(const char* what, const std::string& sizes, const std::vector<std::pair<DevBuf*, size_t> >& wanted) {
+    size_t bytes = 0;
+    for (const auto& w : wanted) bytes += w.second;
+    try {
+        for (const auto& w : wanted) w.first->alloc(w.second);
+    } catch (const Error& e) {
+        throw Error(SCG_ERR_DEVICE, std::string("cannot allocate the device buffers of ") + what + " (" + sizes + ", " + std::to_string(bytes) +
+                                        " bytes): " + e.what());
+    }
+}
+
+} // namespace
+
+void compact_cells_on_device(const int32_t* d_cells, int32_t n0, int32_t n1, ComboList& out) {
+    out.keys.clear();
+    out.counts.clear();
+    if (n0 <= 0 || n1 <= 0) return;
+    const uint64_t n_cells = static_cast<uint64_t>(n0) * static_cast<uint64_t>(n1);
+    const uint64_t tiles = scg::compact_tiles(n_cells);
+    if (tiles > static_cast<uint64_t>(INT32_MAX)) {
+        throw Error(SCG_ERR_UNSUPPORTED, "a dense grid of " + std::to_string(n_cells) + " cells is beyond the device compaction (" +
+                                             std::to_string(INT32_MAX) + " tiles of " + std::to_string(SCG_COMPACT_TILE_CELLS) + " cells)");
+    }
+    const std::string grid = std::to_string(n0) + " x " + std::to_string(n1) + " cells";
+    OwnStream st;
+    DevBuf tile_counts, tile_offsets, scratch, keys, counts;
+    const size_t scratch_bytes = scg::compact_scan_scratch_bytes(n_cells);
+    alloc_all("the combination compaction", grid, {{&tile_counts, (tiles + 1) * sizeof(unsigned long long)},
+                                                   {&tile_offsets, (tiles + 1) * sizeof(unsigned long long)}, {&scratch, scratch_bytes}});
+    HIP_CHECK(scg::launch_compact_count(d_cells, n_cells, tile_counts.as<unsigned long long>(), tile_offsets.as<unsigned long long>(), scratch.p,
+                                        scratch_bytes, st.s));
+    // the one number the second pass's buffers depend on
+    unsigned long long k = 0;
+    HIP_CHECK(hipMemcpyAsync(&k, tile_offsets.as<unsigned long long>() + tiles, sizeof(k), hipMemcpyDeviceToHost, st.s));
+    HIP_CHECK(hipStreamSynchronize(st.s));
+    if (k == 0) return;
+    if (k > n_cells) throw Error(SCG_ERR_DEVICE, "internal: combination compaction: more pairs than cells");
+    alloc_all("the combination compaction", grid + ", " + std::to_string(k) + " pairs", {{&keys, k * sizeof(uint64_t)}, {&counts, k * sizeof(int32_t)}});
+    HIP_CHECK(scg::launch_compact_scatter(d_cells, n_cells, static_cast<uint32_t>(n1), tile_offsets.as<unsigned long long>(), keys.as<uint64_t>(),
+                                          counts.as<int32_t>(), st.s));
+    out.keys.resize(k);
+    out.counts.resize(k);
+    HIP_CHECK(hipMemcpyAsync(out.keys.data(), keys.p, k * sizeof(uint64_t), hipMemcpyDeviceToHost, st.s));
+    HIP_CHECK(hipMemcpyAsync(out.counts.data(), counts.p, k * sizeof(int32_t), hipMemcpyDeviceToHost, st.s));
+    HIP_CHECK(hipStreamSynchronize(st.s));
+}
+
+void combo_list_of_plan(scg_plan* P, ComboList& out) {
+    DeviceGuard g(P->device);
+    read_counters(P, nullptr);                              // (the oversize-read flag, as before every read-out)
+    if (!P->sparse) {
+        compact_cells_on_device(P->counters, P->n_pool[0], P->n_pool[1], out);
+        return;
+    }
+    const std::unordered_map<uint64_t, int64_t> m = sparse_merged(std::vector<scg_plan*>(1, P));
+    std::vector<std::pair<uint64_t, int64_t> > rows(m.begin(), m.end());
+    std::sort(rows.begin(), rows.end());
+    out.keys.resize(rows.size());
+    out.counts.resize(rows.size());
+    for (size_t j = 0; j < rows.size(); ++j) {
+        if (rows[j].second > static_cast<int64_t>(INT32_MAX)) throw Error(SCG_ERR_INVALID, "a count exceeds the 32-bit range of the count vectors");
+        out.keys[j] = rows[j].first;
+        out.counts[j] = static_cast<int32_t>(rows[j].second);
+    }
+}
+
+void combo_list_of_outputs(const int32_t* idx, const int32_t* freq, int64_t k, ComboList& out) {
+    out.keys.resize(static_cast<size_t>(k));
+    out.counts.assign(freq, freq + k);
+    for (int64_t j = 0; j < k; ++j) {
+        if (idx[2 * j] < 0 || idx[2 * j + 1] < 0) throw Error(SCG_ERR_INVALID, "negative barcode index in a combination");
+        out.keys[static_cast<size_t>(j)] = (static_cast<uint64_t>(static_cast<uint32_t>(idx[2 * j])) << 32) | static_cast<uint32_t>(idx[2 * j + 1]);
+    }
+}
+
+void empty_combo_matrix(int32_t n_files, int32_t** indices_out, int64_t* k_out, int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out) {
+    OutPair<int32_t, int64_t> head(1, static_cast<size_t>(n_files) + 1);
+    OutPair<int32_t, int32_t> body(1, 1);
+    head.a[0] = 0; body.a[0] = 0; body.b[0] = 0;
+    for (int32_t f = 0; f <= n_files; ++f) head.b[f] = 0;
+    head.release(indices_out, col_ptr_out);
+    body.release(rows_out, freq_out);
+    *k_out = 0;
+}
+
+void combine_lists(const std::vector<ComboList>& lists, bool sorted_unique, int device, int32_t** indices_out, int64_t* k_out,
+                   int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out) {
+    const size_t n_files = lists.size();
+    uint64_t n = 0;
+    size_t longest = 0;
+    for (const ComboList& l : lists) { n += l.keys.size(); longest = std::max(longest, l.keys.size()); }
+    if (n > 0xFFFFFFFFull) {
+        throw Error(SCG_ERR_UNSUPPORTED, "the files hold " + std::to_string(n) + " combinations in all: more than the 4294967295 one union takes");
+    }
+    if (n == 0) {
+        empty_combo_matrix(static_cast<int32_t>(n_files), indices_out, k_out, col_ptr_out, rows_out, freq_out);
+        return;
+    }
+    std::vector<uint64_t> all_keys(n);
+    std::vector<int32_t> all_counts(n);
+    std::vector<size_t> start(n_files + 1, 0);
+    for (size_t f = 0; f < n_files; ++f) {
+        std::copy(lists[f].keys.begin(), lists[f].keys.end(), all_keys.begin() + static_cast<long>(start[f]));
+        std::copy(lists[f].counts.begin(), lists[f].counts.end(), all_counts.begin() + static_cast<long>(start[f]));
+        start[f + 1] = start[f] + lists[f].keys.size();
+    }
+
+    DeviceGuard g(device);
+    OwnStream st;
+    // keys: the files' lists back to back, every list ascending (as given, or sorted here with its counts in vals)
+    DevBuf keys, sorted, unique, run_lengths, runs, rows, flags, scratch, raw_keys, raw_vals, vals;
+    const size_t scratch_bytes = std::max(scg::sort_rle_scratch_bytes(n), sorted_unique ? size_t(0) : scg::sort_pairs_scratch_bytes(longest));
+    std::vector<std::pair<DevBuf*, size_t> > wanted = {
+        {&keys, n * sizeof(uint64_t)}, {&sorted, n * sizeof(uint64_t)}, {&unique, n * sizeof(uint64_t)}, {&run_lengths, n * sizeof(uint32_t)},
+        {&runs, sizeof(uint32_t)}, {&rows, n * sizeof(int32_t)}, {&flags, 2 * sizeof(int32_t)}, {&scratch, scratch_bytes}};
+    if (!sorted_unique) {
+        wanted.push_back({&raw_keys, n * sizeof(uint64_t)});
+        wanted.push_back({&raw_vals, n * sizeof(int32_t)});
+        wanted.push_back({&vals, n * sizeof(int32_t)});
+    }
+    alloc_all("the union of the files' combinations", std::to_string(n) + " combinations of " + std::to_string(n_files) + " files", wanted);
+    int32_t* const not_found = flags.as<int32_t>();         // flags[0]: a key without a row; flags[1]: a repeat within one list
+    int32_t* const repeated = flags.as<int32_t>() + 1;
+    HIP_CHECK(hipMemsetAsync(flags.p, 0, 2 * sizeof(int32_t), st.s));
+    if (sorted_unique) {
+        HIP_CHECK(hipMemcpyAsync(keys.p, all_keys.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, st.s));
+    } else {
+        HIP_CHECK(hipMemcpyAsync(raw_keys.p, all_keys.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, st.s));
+        HIP_CHECK(hipMemcpyAsync(raw_vals.p, all_counts.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, st.s));
+        for (size_t f = 0; f < n_files; ++f) {
+            const size_t len = start[f + 1] - start[f];
+            if (len == 0) continue;
+            HIP_CHECK(scg::launch_sort_pairs(raw_keys.as<uint64_t>() + start[f], keys.as<uint64_t>() + start[f], raw_vals.as<int32_t>() + start[f],
+                                             vals.as<int32_t>() + start[f], len, scratch.p, scratch_bytes, st.s));
+            HIP_CHECK(scg::launch_flag_equal_neighbours(keys.as<uint64_t>() + start[f], len, repeated, st.s));
+        }
+    }
+    HIP_CHECK(scg::launch_sort_rle(keys.as<uint64_t>(), sorted.as<uint64_t>(), n, unique.as<uint64_t>(), run_lengths.as<uint32_t>(), runs.as<uint32_t>(),
+                                   scratch.p, scratch_bytes, st.s));
+    HIP_CHECK(scg::launch_union_rows(keys.as<uint64_t>(), n, unique.as<uint64_t>(), runs.as<uint32_t>(), rows.as<int32_t>(), not_found, st.s));
+    uint32_t n_unique = 0;
+    int32_t flagged[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(&n_unique, runs.p, sizeof(n_unique), hipMemcpyDeviceToHost, st.s));
+    HIP_CHECK(hipMemcpyAsync(flagged, flags.p, sizeof(flagged), hipMemcpyDeviceToHost, st.s));
+    HIP_CHECK(hipStreamSynchronize(st.s));                  // the one wait of the union; the results are copied behind it
+    if (flagged[1]) throw Error(SCG_ERR_INVALID, "barcode combinations should be unique within each DataFrame in '...'");   // R/combineComboCounts.R:50-52
+    if (flagged[0]) throw Error(SCG_ERR_DEVICE, "internal: union of combinations: a combination has no row");
+    if (n_unique > static_cast<uint32_t>(INT32_MAX)) {
+        throw Error(SCG_ERR_INVALID, "number of distinct barcode combinations exceeds the 32-bit range of the row indices");
+    }
+    const size_t K = n_unique;
+    std::vector<uint64_t> union_keys(K);
+    HIP_CHECK(hipMemcpy(union_keys.data(), unique.p, K * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    OutPair<int32_t, int64_t> head(2 * K + 1, n_files + 1);
+    OutPair<int32_t, int32_t> body(n + 1, n + 1);
+    for (size_t k = 0; k < K; ++k) {
+        head.a[2 * k] = static_cast<int32_t>(union_keys[k] >> 32);
+        head.a[2 * k + 1] = static_cast<int32_t>(union_keys[k] & 0xFFFFFFFFu);
+    }
+    for (size_t f = 0; f <= n_files; ++f) head.b[f] = static_cast<int64_t>(start[f]);
+    HIP_CHECK(hipMemcpy(body.a, rows.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (sorted_unique) std::memcpy(body.b, all_counts.data(), n * sizeof(int32_t));
+    else HIP_CHECK(hipMemcpy(body.b, vals.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    head.release(indices_out, col_ptr_out);
+    body.release(rows_out, freq_out);
+    *k_out = static_cast<int64_t>(K);
 }
 
 void with_per_file_outputs(int32_t** idx_out, int32_t** freq_out, int64_t* k_out, int32_t n_files, const std::function<void()>& body) {

@@ -383,3 +383,88 @@ Rcpp::List count_random_barcodes_files(Rcpp::CharacterVector paths, std::string 
     }
     return Rcpp::List::create(sequences, counts, totals);
 }
+
+namespace {
+// The combination matrix as libscg hands it out (include/scg.h, "Combination counts of many files as one matrix"): the
+// union's 2 x K indices and the files' columns in compressed form.  Released when this goes out of scope.
+struct CombinationMatrix {
+    int32_t *idx = nullptr, *rows = nullptr, *freq = nullptr;
+    int64_t* col_ptr = nullptr;
+    int64_t k = 0;
+    CombinationMatrix() {}
+    CombinationMatrix(const CombinationMatrix&) = delete;
+    CombinationMatrix& operator=(const CombinationMatrix&) = delete;
+    ~CombinationMatrix() { scg_free(idx); scg_free(rows); scg_free(freq); scg_free(col_ptr); }
+    Rcpp::IntegerMatrix indices() const { return combination_indices(idx, k); }
+    // K x n_files, zero-filled; column f = file f: the out.counts of R/combineComboCounts.R:45-54
+    Rcpp::IntegerMatrix counts(R_xlen_t n_files) const {
+        Rcpp::IntegerMatrix m((int)k, n_files);
+        for (R_xlen_t c = 0; c < n_files; ++c) {
+            int* column = m.column_begin(c);
+            for (int64_t j = col_ptr[c]; j < col_ptr[c + 1]; ++j) column[rows[j]] = freq[j];
+        }
+        return m;
+    }
+};
+}
+
+// matrixOfComboBarcodes after its combineComboCounts: List(indices 2 x K, counts K x n_files, totals).  Rows are sorted by
+// (first index, second index); with indices=FALSE the R wrapper reorders them by the barcode strings.
+//[[Rcpp::export(rng=false)]]
+Rcpp::List count_combo_barcodes_single_matrix(Rcpp::CharacterVector paths, std::string constant, int strand, Rcpp::List pool,
+                                              int mismatches, bool use_first, int nthreads) {
+    if (pool.size() != 2) Rcpp::stop("currently expecting only 2 variable regions for single-end combinatorial barcodes");
+    Rcpp::CharacterVector c0(pool[0]), c1(pool[1]);
+    auto f = borrow(paths), p0 = borrow(c0), p1 = borrow(c1);
+    CombinationMatrix found;
+    Rcpp::IntegerVector totals(paths.size());
+    char err[1024];
+    check(scg_count_combo_barcodes_single_matrix(f.data(), (int32_t)f.size(), constant.c_str(), strand, p0.data(), (int32_t)p0.size(),
+                                                 p1.data(), (int32_t)p1.size(), mismatches, use_first, nthreads,
+                                                 &found.idx, &found.k, &found.col_ptr, &found.rows, &found.freq, totals.begin(), err, sizeof(err)), err);
+    return Rcpp::List::create(found.indices(), found.counts(paths.size()), totals);
+}
+
+// matrixOfPairedComboBarcodes after its combineComboCounts: List(indices, counts, totals, barcode-1-only, barcode-2-only).
+//[[Rcpp::export(rng=false)]]
+Rcpp::List count_combo_barcodes_paired_matrix(Rcpp::CharacterVector paths1, std::string constant1, bool reverse1, int mismatches1,
+                                              Rcpp::CharacterVector pool1,
+                                              Rcpp::CharacterVector paths2, std::string constant2, bool reverse2, int mismatches2,
+                                              Rcpp::CharacterVector pool2, bool randomized, bool use_first, int nthreads) {
+    if (paths1.size() != paths2.size()) Rcpp::stop("'paths1' and 'paths2' should be of the same length");
+    auto f1 = borrow(paths1), f2 = borrow(paths2), p1 = borrow(pool1), p2 = borrow(pool2);
+    CombinationMatrix found;
+    Rcpp::IntegerVector totals(paths1.size()), b1(paths1.size()), b2(paths1.size());
+    char err[1024];
+    check(scg_count_combo_barcodes_paired_matrix(f1.data(), constant1.c_str(), reverse1, mismatches1, p1.data(), (int32_t)p1.size(),
+                                                 f2.data(), constant2.c_str(), reverse2, mismatches2, p2.data(), (int32_t)p2.size(),
+                                                 (int32_t)f1.size(), randomized, use_first, nthreads,
+                                                 &found.idx, &found.k, &found.col_ptr, &found.rows, &found.freq,
+                                                 totals.begin(), b1.begin(), b2.begin(), err, sizeof(err)), err);
+    return Rcpp::List::create(found.indices(), found.counts(paths1.size()), totals, b1, b2);
+}
+
+// combineComboCounts (R/combineComboCounts.R:31-57) for lists R already holds, in the form its own first step gives them:
+// the DataFrames bound together -- `first` and `second` (0-based indices) and `counts` of all of them back to back -- and
+// `sizes`, the number of rows of each.  List(indices 2 x K, counts K x length(sizes)).
+//[[Rcpp::export(rng=false)]]
+Rcpp::List combine_combinations(Rcpp::IntegerVector first, Rcpp::IntegerVector second, Rcpp::IntegerVector counts, Rcpp::IntegerVector sizes) {
+    if (first.size() != second.size() || first.size() != counts.size()) Rcpp::stop("'first', 'second' and 'counts' should be of the same length");
+    const R_xlen_t n_files = sizes.size();
+    std::vector<int32_t> pairs(2 * (size_t)first.size() + 2);
+    for (R_xlen_t i = 0; i < first.size(); ++i) { pairs[2 * i] = first[i]; pairs[2 * i + 1] = second[i]; }
+    std::vector<const int32_t*> idx(n_files + 1), freq(n_files + 1);
+    std::vector<int64_t> k(n_files + 1);
+    R_xlen_t at = 0;
+    for (R_xlen_t f = 0; f < n_files; ++f) {
+        if (sizes[f] < 0 || sizes[f] > first.size() - at) Rcpp::stop("'sizes' should add up to the number of combinations");
+        idx[f] = pairs.data() + 2 * at; freq[f] = counts.begin() + at; k[f] = sizes[f];
+        at += sizes[f];
+    }
+    if (at != first.size()) Rcpp::stop("'sizes' should add up to the number of combinations");
+    CombinationMatrix found;
+    char err[1024];
+    check(scg_combine_combinations(idx.data(), freq.data(), k.data(), (int32_t)n_files,
+                                   &found.idx, &found.k, &found.col_ptr, &found.rows, &found.freq, err, sizeof(err)), err);
+    return Rcpp::List::create(found.indices(), found.counts(n_files));
+}
