@@ -117,6 +117,22 @@ int scg_count_combo_barcodes_single(const char* path, const char* constant, int 
                                     int32_t** indices_out, int32_t** freq_out, int64_t* k_out,
                                     int32_t* total_out, char* err, size_t errcap);
 
+/* Combinations of barcodes over any number of variable regions: kaori::CombinatorialBarcodesSingleEnd<max_size, V>
+ * (inst/include/kaori/handlers/CombinatorialBarcodesSingleEnd.hpp:149-258) for V = n_regions, which the reference's R
+ * layer instantiates for V = 2 only (src/count_combo_barcodes_single.cpp:44-46).  pools: n_regions arrays of n_pools[r]
+ * strings, pool r for variable region r of the forward template; every combination of one barcode per pool counts, with
+ * one mismatch budget shared by the constant bases and all regions.  On success *indices_out is a malloc'd
+ * n_regions x K column-major matrix of 0-based pool indices whose columns are sorted by (first, ..., last), *freq_out the
+ * K frequencies; release both with scg_free.  The reader is opened before the arguments are checked.  The handler's
+ * errors in its constructor's order: "expected <n_regions> variable regions in the constant template", "length of
+ * variable region <i> (..) should be the same as its sequences (..)", "negative number of mismatches".  This engine:
+ * 1 to 8 regions, and pool sizes whose product is below 2^63 (SCG_ERR_UNSUPPORTED otherwise). */
+int scg_count_combo_barcodes_regions(const char* path, const char* constant, int strand,
+                                     const char* const* const* pools, const int32_t* n_pools, int32_t n_regions,
+                                     int mismatches, int use_first, int nthreads,
+                                     int32_t** indices_out, int32_t** freq_out, int64_t* k_out,
+                                     int32_t* total_out, char* err, size_t errcap);
+
 /* countDualBarcodes hot path, paired-end.  Replaces src/count_dual_barcodes.cpp:74-117,
  * non-diagnostic branch (:38-51).  pool1[i] / pool2[i] form valid pair i; counts_out has n_pool
  * entries.  diagnostics must be 0 here: the include.invalid=TRUE branch returns more outputs and
@@ -229,6 +245,15 @@ int scg_count_combo_barcodes_single_files(const char* const* paths, int32_t n_fi
                                           int mismatches, int use_first, int nthreads,
                                           int32_t** indices_out, int32_t** freq_out, int64_t* k_out,
                                           int32_t* totals_out, char* err, size_t errcap);
+
+/* The same for scg_count_combo_barcodes_regions: entry f receives file f's malloc'd n_regions x K_f matrix, K_f
+ * frequencies and K_f.  The first file's reader comes first, then the argument errors.  There is no merged matrix over
+ * files for more than two regions (scg_count_combo_barcodes_single_matrix and scg_combine_combinations are 2 x K). */
+int scg_count_combo_barcodes_regions_files(const char* const* paths, int32_t n_files, const char* constant, int strand,
+                                           const char* const* const* pools, const int32_t* n_pools, int32_t n_regions,
+                                           int mismatches, int use_first, int nthreads,
+                                           int32_t** indices_out, int32_t** freq_out, int64_t* k_out,
+                                           int32_t* totals_out, char* err, size_t errcap);
 
 /* counts_out: n_pool x n_files, column-major; totals_out: n_files (the `npairs` of R/countDualBarcodes.R:236). */
 int scg_count_dual_barcodes_files(const char* const* paths1, const char* constant1, int reverse1, int mismatches1,
@@ -464,6 +489,18 @@ int scg_plan_dual_single_end(scg_plan** plan_out, const char* constant, int stra
                              const char* const* const* pools, const int32_t* n_pools, int32_t n_regions,
                              int mismatches, int use_first, int device, char* err, size_t errcap);
 
+/* Plan for scg_count_combo_barcodes_regions (combinations over n_regions variable regions): its arguments and argument
+ * errors, raised before any device work.  Counted with scg_count_batch, read with scg_plan_read_combinations, which
+ * returns a malloc'd n_regions x K matrix (scg_plan_num_regions sizes it); scg_plan_read gives the total.  The counters
+ * are a flat histogram over the pools, cell = ((i_0 * n_1 + i_1) * n_2 + ...) + i_last, up to the dense limit
+ * ($SCG_DENSE_CELLS, default 2^26 cells); beyond it the plan keeps sorted runs of 64-bit keys and no counters. */
+int scg_plan_combo_regions(scg_plan** plan_out, const char* constant, int strand,
+                           const char* const* const* pools, const int32_t* n_pools, int32_t n_regions,
+                           int mismatches, int use_first, int device, char* err, size_t errcap);
+
+/* Variable regions of the plan's (first) template; for scg_plan_combo_regions the rows of its combination matrix. */
+int32_t scg_plan_num_regions(const scg_plan* plan);
+
 /* Plan for countPairedComboBarcodes: counted with scg_count_batch_paired, read with
  * scg_plan_read_diagnostics (counts_out = NULL; the "invalid" outputs are the combinations). */
 int scg_plan_paired_combo(scg_plan** plan_out,
@@ -558,7 +595,9 @@ int scg_plan_read(scg_plan* plan, int32_t* counts_out, int64_t* total_out, void*
  * -- a malloc'd 2 x K matrix of 0-based indices sorted by (first, second), K frequencies (release both with scg_free) --
  * whether the plan keeps a dense histogram (n_pool0 x n_pool1 <= 2^26 cells: scg_plan_read + scg_combo_compact give the
  * same) or, beyond that, sorts and run-length encodes the combinations of every batch on the device and merges the runs
- * (scg_plan_num_counters is 0 then).  Synchronises `stream`. */
+ * (scg_plan_num_counters is 0 then).  Synchronises `stream`.
+ * Plans of scg_plan_combo_regions: an n_regions x K matrix sorted by (first, ..., last) and K frequencies; a dense
+ * histogram is compacted on the device, as (all pools but the last) x (last pool) cells, and the keys decoded here. */
 int scg_plan_read_combinations(scg_plan* plan, int32_t** indices_out, int32_t** freq_out, int64_t* k_out, int64_t* total_out,
                                void* stream, char* err, size_t errcap);
 

@@ -14,7 +14,7 @@ from .api import (  # noqa: F401
     count_single_barcodes_files, count_combo_barcodes_single_files, count_dual_barcodes_files, count_dual_barcodes_single_end,
     count_dual_barcodes_diagnostics_files, count_dual_barcodes_single_end_files, count_dual_barcodes_single_end_diagnostics_files,
     count_combo_barcodes_paired_files, count_single_barcodes_paired, count_single_barcodes_paired_files, count_random_barcodes, count_random_barcodes_files, match_barcodes, parse_fastq,
-    assign_single_barcodes,
+    assign_single_barcodes, count_combo_barcodes_regions, count_combo_barcodes_regions_files,
     combine_combinations, count_combo_barcodes_single_matrix, count_combo_barcodes_paired_matrix, combo_compact_device,
 )
 from .engine import Assignment, Plan, combo_compact, upload_reads  # noqa: F401

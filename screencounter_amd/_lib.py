@@ -72,6 +72,8 @@ SIGNATURES = {
     "scg_count_combo_barcodes_single": (INT, [STR, STR, INT, *POOL, *POOL, INT, INT, INT, *COMBOS, i32_p, *ERR]),
     "scg_count_dual_barcodes": (INT, [STR, STR, INT, INT, c_str_p, STR, STR, INT, INT, c_str_p, I32,
                                       INT, INT, INT, INT, i32_p, i32_p, *ERR]),
+    "scg_count_combo_barcodes_regions": (INT, [STR, STR, INT, *POOLS, INT, INT, INT, *COMBOS, i32_p, *ERR]),
+    "scg_count_combo_barcodes_regions_files": (INT, [c_str_p, I32, STR, INT, *POOLS, INT, INT, INT, *COMBOS, i32_p, *ERR]),
     "scg_count_single_barcodes_paired": (INT, [STR, STR, STR, INT, *POOL, INT, INT, INT, i32_p, i32_p, *ERR]),
     "scg_count_single_barcodes_paired_files": (INT, [c_str_p, c_str_p, I32, STR, INT, *POOL, INT, INT, INT, i32_p, i32_p, *ERR]),
     "scg_match_barcodes": (INT, [*POOL, *POOL, INT, INT, i32_p, i32_p, *ERR]),
@@ -101,6 +103,8 @@ SIGNATURES = {
     "scg_plan_single": (INT, [PLAN_OUT, STR, INT, *POOL, INT, INT, INT, *ERR]),
     "scg_plan_single_paired": (INT, [PLAN_OUT, STR, INT, *POOL, INT, INT, INT, *ERR]),
     "scg_plan_combo": (INT, [PLAN_OUT, STR, INT, *POOL, *POOL, INT, INT, INT, *ERR]),
+    "scg_plan_combo_regions": (INT, [PLAN_OUT, STR, INT, *POOLS, INT, INT, INT, *ERR]),
+    "scg_plan_num_regions": (I32, [PTR]),
     "scg_plan_dual": (INT, [PLAN_OUT, STR, INT, INT, c_str_p, STR, INT, INT, c_str_p, I32, INT, INT, INT, INT, *ERR]),
     "scg_count_dual_barcodes_diagnostics": (INT, [STR, STR, INT, INT, c_str_p, STR, STR, INT, INT, c_str_p, I32,
                                                   INT, INT, INT, i32_p, *COMBOS, i32_p, i32_p, i32_p, *ERR]),
@@ -220,10 +224,11 @@ def pool(strings):
 
 
 @contextlib.contextmanager
-def per_file_combo_outputs(L, n: int):
+def per_file_combo_outputs(L, n: int, rows: int = 2):
     """The caller-allocated arrays of n entries for the malloc'd combinations of a many-files entry (int32_t** indices_out,
     int32_t** freq_out, int64_t* k_out).  `with ... as (outputs, take)`: pass `*outputs` to the call; after it, take() is a
     list of n (indices int32[2, K_f], freq int32[K_f]), fresh arrays that own their memory, (2, 0) and (0,) where K_f is 0.
+    rows: the rows of the index matrices where they are not 2 (combinations over `rows` variable regions).
     Leaving the block frees every pointer the C side handed out, whatever happened inside: a call that failed, an
     exception while copying."""
     idx, freq, ks = (i32_p * max(n, 1))(), (i32_p * max(n, 1))(), (C.c_int64 * max(n, 1))()
@@ -231,8 +236,8 @@ def per_file_combo_outputs(L, n: int):
     def copies(f):
         K = int(ks[f])
         if K == 0:                                   # (nothing to read: the pointers are not looked at)
-            return np.zeros((2, 0), dtype=np.int32), np.zeros(0, dtype=np.int32)
-        return np.ctypeslib.as_array(idx[f], shape=(K, 2)).T.copy(), np.ctypeslib.as_array(freq[f], shape=(K,)).copy()
+            return np.zeros((rows, 0), dtype=np.int32), np.zeros(0, dtype=np.int32)
+        return np.ctypeslib.as_array(idx[f], shape=(K, rows)).T.copy(), np.ctypeslib.as_array(freq[f], shape=(K,)).copy()
     try:
         yield (idx, freq, ks), lambda: [copies(f) for f in range(n)]
     finally:
@@ -242,10 +247,10 @@ def per_file_combo_outputs(L, n: int):
 
 
 @contextlib.contextmanager
-def combo_outputs(L):
+def combo_outputs(L, rows: int = 2):
     """The same for the three outputs of an entry that returns one set of combinations -- the per-file arrays with one
-    entry: take() -> (indices int32[2, K], freq int32[K])."""
-    with per_file_combo_outputs(L, 1) as (outputs, take):
+    entry: take() -> (indices int32[rows, K], freq int32[K])."""
+    with per_file_combo_outputs(L, 1, rows) as (outputs, take):
         yield outputs, lambda: take()[0]
 
 

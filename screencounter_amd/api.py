@@ -66,6 +66,20 @@ def count_combo_barcodes_single(path: str, constant: str, strand: int, pool: Seq
     return idx, freq, int(total.value)
 
 
+def count_combo_barcodes_regions(path: str, constant: str, strand: int, pools: Sequence[Sequence[str]], mismatches: int,
+                                 use_first: bool, nthreads: int = 1):
+    """Combinations over len(pools) variable regions (kaori::CombinatorialBarcodesSingleEnd for any number of regions, 1 to 8
+    here) -> (indices int32[len(pools), K] 0-based, sorted by (first, ..., last), freq int32[K], total)."""
+    L, err = _lib.load(), errbuf()
+    total = C.c_int32(0)
+    rows, sizes, _keep = _lib.cstr_matrix(pools)
+    with combo_outputs(L, max(len(pools), 1)) as (combos, take):
+        check(L.scg_count_combo_barcodes_regions(_path(path), constant.encode(), int(strand), rows, sizes, len(pools),
+                                                 int(mismatches), int(bool(use_first)), int(nthreads), *combos, C.byref(total), err, ERRCAP), err)
+        idx, freq = take()
+    return idx, freq, int(total.value)
+
+
 def count_single_barcodes_paired(path1: str, path2: str, constant: str, strand: int, pool: Sequence[str], mismatches: int, use_first: bool,
                                  nthreads: int = 1):
     """kaori::SingleBarcodePairedEnd (handlers/SingleBarcodePairedEnd.hpp:93-124) over two files: the barcode of a pair is
@@ -217,6 +231,17 @@ def count_combo_barcodes_single_files(paths: Sequence[str], constant: str, stran
     with _files_call(devices, paths) as (n, (farr,), (totals,)), per_file_combo_outputs(L, n) as (combos, take):
         check(L.scg_count_combo_barcodes_single_files(farr, n, constant.encode(), int(strand), *_lib.pool(pool[0]), *_lib.pool(pool[1]),
                                                       int(mismatches), int(bool(use_first)), int(nthreads), *combos, totals, err, ERRCAP), err)
+        return [(idx, freq, total) for (idx, freq), total in zip(take(), totals[:n])]
+
+
+def count_combo_barcodes_regions_files(paths: Sequence[str], constant: str, strand: int, pools: Sequence[Sequence[str]], mismatches: int,
+                                       use_first: bool, nthreads: int = 1, devices=None):
+    """scg_count_combo_barcodes_regions_files -> list of (indices int32[len(pools), K], freq int32[K], total), one per file."""
+    L, err = _lib.load(), errbuf()
+    rows, sizes, _keep = _lib.cstr_matrix(pools)
+    with _files_call(devices, paths) as (n, (farr,), (totals,)), per_file_combo_outputs(L, n, max(len(pools), 1)) as (combos, take):
+        check(L.scg_count_combo_barcodes_regions_files(farr, n, constant.encode(), int(strand), rows, sizes, len(pools),
+                                                       int(mismatches), int(bool(use_first)), int(nthreads), *combos, totals, err, ERRCAP), err)
         return [(idx, freq, total) for (idx, freq), total in zip(take(), totals[:n])]
 
 

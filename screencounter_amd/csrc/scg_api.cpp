@@ -283,6 +283,13 @@ int scg_plan_combo(scg_plan** plan_out, const char* constant, int strand, const 
     });
 }
 
+int scg_plan_combo_regions(scg_plan** plan_out, const char* constant, int strand, const char* const* const* pools, const int32_t* n_pools,
+                           int32_t n_regions, int mismatches, int use_first, int device, char* err, size_t errcap) {
+    return new_plan(plan_out, device, err, errcap, [&] {
+        return compile_combo_regions(constant, strand, pools, n_pools, n_regions, mismatches, use_first);
+    });
+}
+
 int scg_plan_dual(scg_plan** plan_out, const char* constant1, int reverse1, int mismatches1, const char* const* pool1,
                   const char* constant2, int reverse2, int mismatches2, const char* const* pool2,
                   int32_t n_pool, int randomized, int use_first, int diagnostics, int device, char* err, size_t errcap) {
@@ -335,6 +342,11 @@ void scg_plan_destroy(scg_plan* plan) {
 }
 
 int64_t scg_plan_num_counters(const scg_plan* plan) { return plan ? plan->n_counters : 0; }
+
+int32_t scg_plan_num_regions(const scg_plan* plan) {
+    if (!plan) return 0;
+    return plan->kind == scg_plan::COMBO_REGIONS ? plan->n_regions : plan->ht1.t.nreg;
+}
 
 int32_t* scg_plan_device_counters(scg_plan* plan) { return plan ? plan->counters : nullptr; }
 
@@ -425,7 +437,7 @@ int scg_plan_read_combinations(scg_plan* plan, int32_t** indices_out, int32_t** 
                                void* stream, char* err, size_t errcap) {
     return guarded(err, errcap, [&] {
         if (!plan || !indices_out || !freq_out || !k_out) throw Error(SCG_ERR_INVALID, "null argument");
-        if (plan->kind != scg_plan::COMBO) throw Error(SCG_ERR_INVALID, "not a combination plan");
+        if (plan->kind != scg_plan::COMBO && plan->kind != scg_plan::COMBO_REGIONS) throw Error(SCG_ERR_INVALID, "not a combination plan");
         DeviceGuard g(plan->device);
         HIP_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
         result_combinations(std::vector<scg_plan*>(1, plan), indices_out, freq_out, k_out, nullptr);
@@ -495,6 +507,21 @@ int scg_count_combo_barcodes_single(const char* path, const char* constant, int 
         scg::FastqStream fq(path);
         auto set = compile_and_count_single_end(path, fq, nthreads, [&] {
             return compile_combo(constant, strand, pool0, n_pool0, pool1, n_pool1, mismatches, use_first);
+        });
+        result_combinations(set->all(), indices_out, freq_out, k_out, total_out);
+    });
+}
+
+int scg_count_combo_barcodes_regions(const char* path, const char* constant, int strand,
+                                     const char* const* const* pools, const int32_t* n_pools, int32_t n_regions,
+                                     int mismatches, int use_first, int nthreads,
+                                     int32_t** indices_out, int32_t** freq_out, int64_t* k_out, int32_t* total_out,
+                                     char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (!path || !indices_out || !freq_out || !k_out || !total_out) throw Error(SCG_ERR_INVALID, "null argument");
+        scg::FastqStream fq(path);                                           // the reader first, as in the two-region entry
+        auto set = compile_and_count_single_end(path, fq, nthreads, [&] {
+            return compile_combo_regions(constant, strand, pools, n_pools, n_regions, mismatches, use_first);
         });
         result_combinations(set->all(), indices_out, freq_out, k_out, total_out);
     });
@@ -646,6 +673,19 @@ int scg_count_combo_barcodes_single_files(const char* const* paths, int32_t n_fi
         if (n_files < 0 || (n_files > 0 && (!paths || !indices_out || !freq_out || !k_out || !totals_out))) throw Error(SCG_ERR_INVALID, "null argument");
         count_files_into(FileLists{paths, nullptr, n_files}, nthreads, Order::FILE0_FIRST, [&] {
             return compile_combo(constant, strand, pool0, n_pool0, pool1, n_pool1, mismatches, use_first);
+        }, ReadOut::COMBINATIONS, PerFile{nullptr, indices_out, freq_out, k_out, totals_out, nullptr, nullptr});
+    });
+}
+
+int scg_count_combo_barcodes_regions_files(const char* const* paths, int32_t n_files, const char* constant, int strand,
+                                           const char* const* const* pools, const int32_t* n_pools, int32_t n_regions,
+                                           int mismatches, int use_first, int nthreads,
+                                           int32_t** indices_out, int32_t** freq_out, int64_t* k_out, int32_t* totals_out,
+                                           char* err, size_t errcap) {
+    return guarded(err, errcap, [&] {
+        if (n_files < 0 || (n_files > 0 && (!paths || !indices_out || !freq_out || !k_out || !totals_out))) throw Error(SCG_ERR_INVALID, "null argument");
+        count_files_into(FileLists{paths, nullptr, n_files}, nthreads, Order::FILE0_THEN_ARGUMENTS, [&] {
+            return compile_combo_regions(constant, strand, pools, n_pools, n_regions, mismatches, use_first);
         }, ReadOut::COMBINATIONS, PerFile{nullptr, indices_out, freq_out, k_out, totals_out, nullptr, nullptr});
     });
 }

@@ -161,7 +161,8 @@ struct ScgCounters {
     // tally_kernel turns the index stream into counts through LDS histograms (scg_kernels.hip).
     int32_t* unit_index;        // nullptr: count with atomics
     // Sparse mode (combination spaces beyond the dense limit: scg_sparse.hip): the combination of read / pair r, or ~0
-    // for none, goes to unit_pair[r] as (first << 32) | second; nothing is added to `base` for it.
+    // for none, goes to unit_pair[r] as (first << 32) | second -- as its mixed-radix key from the kernels over any number of
+    // regions (ScgComboRegionsParams) --; nothing is added to `base` for it.
     uint64_t* unit_pair;        // nullptr: dense cells
     // Diagnostics paths: partial sums of the two single-address tallies (barcode1-only, barcode2-only), one slot
     // per wavefront modulo SCG_HOT_SLOTS, folded into their counters after the launch (hot_fold_kernel).  Even one
@@ -212,6 +213,23 @@ struct ScgComboParams {
     const int32_t* only_if_negative;
     int32_t keep_first;
     int32_t pad;
+};
+
+// Combinations over any number of variable regions (kaori::CombinatorialBarcodesSingleEnd<max_size, num_variable>,
+// handlers/CombinatorialBarcodesSingleEnd.hpp:149-258, for num_variable = nreg in [1, SCG_MAX_REGIONS]).  A read's
+// combination is ONE 64-bit mixed-radix key, key = sum over pools of index[pool] * stride[pool] with the first pool most
+// significant and stride[nreg - 1] = 1: ascending keys are the reference's sort_combinations order, the key is the cell
+// of a dense histogram over the pools, and no lane ever holds an array of indices.
+struct ScgComboRegionsParams {
+    ScgScan scan;
+    const ScgTemplate* tmpl;
+    ScgIndex index[SCG_MAX_REGIONS];      // the pool of forward region r; all in one key class
+    uint64_t stride[SCG_MAX_REGIONS];     // product of the sizes of the pools behind pool r
+    int32_t nreg;
+    int32_t max_mm;
+    int32_t use_first;
+    int32_t fwd, rev;
+    int32_t pad[3];
 };
 
 struct ScgDualParams {

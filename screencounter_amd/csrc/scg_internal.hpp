@@ -258,8 +258,9 @@ struct RandomTally {
 
 struct scg_plan {
     // DUAL_SE_DIAG: single-end dual barcodes, include.invalid=TRUE; SINGLE_PAIRED: one barcode on either mate of a pair
-    // (kaori::SingleBarcodePairedEnd) -- a single plan in everything but the batches it takes
-    enum Kind { SINGLE, COMBO, DUAL, DUAL_SE_DIAG, RANDOM, SINGLE_PAIRED } kind = SINGLE;
+    // (kaori::SingleBarcodePairedEnd) -- a single plan in everything but the batches it takes; COMBO_REGIONS: combinations over
+    // n_regions variable regions (kaori::CombinatorialBarcodesSingleEnd<max_size, n_regions>), pools in hpools / rtab
+    enum Kind { SINGLE, COMBO, DUAL, DUAL_SE_DIAG, RANDOM, SINGLE_PAIRED, COMBO_REGIONS } kind = SINGLE;
     int device = 0;
 
     // host-compiled pieces (valid before any device work)
@@ -273,10 +274,16 @@ struct scg_plan {
     int diagnostics = 0;         // 0 none, 1 include.invalid=TRUE, 2 paired combinations (ScgDualParams::diagnostics)
     bool simple_match = false;   // built by scg_plan_single (kaori::SimpleSingleMatch); a SINGLE plan of scg_plan_dual_single_end is not
     std::vector<int32_t> first1, first2;   // sequence uid -> first pool index (DuplicateAction::FIRST)
+    // COMBO_REGIONS: one pool per forward region, and the mixed-radix strides of a combination's key (ScgComboRegionsParams)
+    int32_t n_regions = 0;
+    std::vector<scg::HostIndex> hpools;
+    std::vector<int32_t> pool_sizes;
+    uint64_t stride[SCG_MAX_REGIONS] = {0, 0, 0, 0, 0, 0, 0, 0};
 
     // device state
     DevBuf d_tmpl1, d_tmpl2;
     DevIndex tab[2];
+    DevIndex rtab[SCG_MAX_REGIONS];   // COMBO_REGIONS
     DevPairTable pairs;
     DevBuf own_counters;
     DevBuf hot;          // diagnostics plans: per-wavefront slots of the two single-address tallies (ScgCounters::hot)
@@ -329,6 +336,7 @@ struct scg_plan {
         if (kind != SINGLE && kind != SINGLE_PAIRED) tab[1].upload(htab[1]);
         if (kind == DUAL_SE_DIAG) { tab_combined.upload(htab_combined); htab_combined = scg::HostIndex(); }
         if (kind == DUAL) pairs.upload(hpairs);
+        for (size_t r = 0; r < hpools.size(); ++r) rtab[r].upload(hpools[r]);
         own_counters.alloc(static_cast<size_t>(std::max<int64_t>(n_counters, 1)) * sizeof(int32_t));   // (plans without counters: random barcodes)
         counters = own_counters.as<int32_t>();
         HIP_CHECK(hipMemset(counters, 0, static_cast<size_t>(std::max<int64_t>(n_counters, 1)) * sizeof(int32_t)));
@@ -354,6 +362,7 @@ struct scg_plan {
         HIP_CHECK(hipStreamSynchronize(nullptr));
         // host copies are no longer needed
         for (auto& h : htab) { h = scg::HostIndex(); }
+        hpools.clear();
         hpairs = scg::HostPairTable();
     }
 
@@ -389,6 +398,8 @@ std::unique_ptr<scg_plan> compile_dual_single_end(const char* constant, int stra
                                                   int mismatches, int use_first);
 std::unique_ptr<scg_plan> compile_combo(const char* constant, int strand, const char* const* pool0, int32_t n0, const char* const* pool1, int32_t n1, int mismatches,
                                         int use_first);
+std::unique_ptr<scg_plan> compile_combo_regions(const char* constant, int strand, const char* const* const* pools, const int32_t* n_pools, int32_t n_regions,
+                                                int mismatches, int use_first);
 std::unique_ptr<scg_plan> compile_dual(const char* constant1, int reverse1, int mismatches1, const char* const* pool1, const char* constant2, int reverse2,
                                        int mismatches2, const char* const* pool2, int32_t n_pool, int randomized, int use_first, int diagnostics = 0);
 std::unique_ptr<scg_plan> compile_dual_single_end_diag(const char* constant, int strand, const char* const* const* pools, const int32_t* n_pools, int32_t n_regions,
@@ -528,6 +539,10 @@ void result_random_matrix(const PlanSet& set, const std::vector<int>& plan_of, c
                           char** sequences_out, int64_t* k_out, int32_t* length_out, int64_t** col_ptr_out, int32_t** rows_out, int32_t** freq_out);
 void combo_compact(const int32_t* cells, int32_t n0, int32_t n1, int32_t** indices_out, int32_t** freq_out, int64_t* k_out);
 void combos_from_sparse(const std::unordered_map<uint64_t, int64_t>& m, int32_t** indices_out, int32_t** freq_out, int64_t* k_out);
+// COMBO_REGIONS plans: the combinations of all `plans` as a malloc'd n_regions x K column-major matrix of pool indices in
+// ascending key order = sorted by (first, ..., last), with their K counts.  Dense plans are compacted on their devices as
+// (product of all pools but the last) x (last pool) cells, stream plans give their merged runs; keys are decoded here.
+void result_combinations_regions(const std::vector<scg_plan*>& plans, int32_t** idx_out, int32_t** freq_out, int64_t* k_out, int32_t* total_out);
 void diagnostics_from_counters(const scg_plan* P, const std::vector<int32_t>& all, int32_t* counts_out, int32_t** idx_out, int32_t** freq_out, int64_t* k_out,
                                int32_t* b1, int32_t* b2, const std::unordered_map<uint64_t, int64_t>* sparse = nullptr);
 // One counted input -> the outputs of its entry point.  `plans`: the plans that counted it -- one per device of a one-file

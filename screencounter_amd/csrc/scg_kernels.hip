@@ -11,6 +11,7 @@
 //   assign_kernel <- the same search, its whole State kept     ../SimpleSingleMatch.hpp:103-140
 //   single_paired_kernel <- SingleBarcodePairedEnd::process   SingleBarcodePairedEnd.hpp:93-124
 //   combo_kernel  <- CombinatorialBarcodesSingleEnd::process   CombinatorialBarcodesSingleEnd.hpp:149-258
+//   combo_regions_kernel <- the same for any num_variable (1 to 8 regions, a run-time value)
 //   dual_kernel   <- DualBarcodesPairedEnd::process            DualBarcodesPairedEnd.hpp:228-381
 // Per-handler vector<int> counters + serial reduce() become device atomics on one int32 array.
 #include <hip/hip_runtime.h>
@@ -343,6 +344,100 @@ __global__ __launch_bounds__(BLOCK) void combo_kernel(ScgComboParams P, ScgReads
     Read rd = get_read(R, i);
     const BestCombo hit = combo_read<W>(P, rd);
     emit_combo(cells, i, hit.found, hit.id[0], hit.id[1], P.n_pool[1]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// combinations over nreg variable regions, nreg a run-time value in [1, SCG_MAX_REGIONS]
+// (CombinatorialBarcodesSingleEnd<max_size, num_variable>::process for any num_variable)
+// ---------------------------------------------------------------------------------------------
+// What a window's look-ups select per lane -- the pool of a region depends on the strand, which differs from lane to lane
+// -- in LDS, once per workgroup, for the reason given above combo_candidate_staged: from LDS the selection is an address.
+struct ComboPools {
+    ScgIndex index[SCG_MAX_REGIONS];
+    uint64_t stride[SCG_MAX_REGIONS];
+};
+
+// EVERY lane of the workgroup calls this; the barrier that makes the copy visible is the caller's (stage_tile's in the
+// staged kernel).  ScgComboRegionsParams keeps `index` and `stride` adjacent, in ComboPools' layout.
+__device__ __forceinline__ void load_combo_pools(ComboPools& pools, const ScgComboRegionsParams& P) {
+    static_assert(sizeof(ComboPools) % 4 == 0, "copied by dwords");
+    static_assert(offsetof(ScgComboRegionsParams, stride) - offsetof(ScgComboRegionsParams, index) == offsetof(ComboPools, stride), "one copy");
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(&P.index[0]);
+    for (unsigned i = threadIdx.x; i < sizeof(ComboPools) / 4; i += blockDim.x) reinterpret_cast<uint32_t*>(&pools)[i] = src[i];
+}
+
+// BestCombo's rule (:225-241) on the mixed-radix key of a combination (ScgComboRegionsParams): equal keys are equal
+// combinations.  Start from {max_mm + 1, 0, false}.
+struct BestKey {
+    int best;
+    uint64_t key;
+    bool found;
+    __device__ __forceinline__ void take(uint64_t cand) { found = true; key = cand; }
+    __device__ __forceinline__ void offer(uint64_t cand, int tot) {
+        if (tot > best) return;
+        if (tot == best) {
+            if (key != cand) found = false;
+        } else {
+            found = true; best = tot; key = cand;
+        }
+    }
+};
+
+// Read i gave the combination `key`, or none: to the key stream (sparse mode) or to its cell of the flat histogram.
+__device__ __forceinline__ void emit_key(const ScgCounters& cells, int64_t i, bool found, uint64_t key) {
+    if (cells.unit_pair) cells.unit_pair[i] = found ? key : ~0ull;
+    else if (found) count_one(cells, (int64_t)key);
+}
+
+// find_match (:149-186) at window p, byte-wise: the regions in scan order, region r in pool `slot`, one budget for all.
+template<class W>
+__device__ __forceinline__ bool combo_regions_candidate(const ScgComboRegionsParams& P, const ComboPools& pools, const Read& rd, int p, bool reverse, int c,
+                                                        uint64_t& key, int& total) {
+    const ScgTemplate* T = P.tmpl;
+    const int nreg = P.nreg;
+    int obs = c;
+    uint64_t k = 0;
+    for (int r = 0; r < nreg; ++r) {
+        const int slot = reverse ? (nreg - 1 - r) : r;      // reverse scan order meets the pools back to front (:111-116)
+        const int start = reverse ? T->rstart[r] : T->fstart[r];
+        const ScgIndex& tab = pools.index[slot];
+        QueryT<W> q = pack_region<W>(rd.p + p + start, tab.len, reverse);
+        int idx, d;
+        index_match<W>(tab, q, P.max_mm - obs, idx, d);      // :168
+        if (idx < 0) return false;
+        obs += d;
+        if (obs > P.max_mm) return false;                    // :173-176
+        k += (uint64_t)(uint32_t)idx * pools.stride[slot];   // :178-182
+    }
+    key = k;
+    total = obs;
+    return true;
+}
+
+template<class W>
+__global__ __launch_bounds__(BLOCK) void combo_regions_kernel(ScgComboRegionsParams P, ScgReads R, int64_t n_reads, ScgCounters cells) {
+    __shared__ ComboPools pools;
+    load_combo_pools(pools, P);
+    __syncthreads();
+    int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n_reads) return;
+    const Read rd = get_read(R, i);
+    const ScgTemplate* T = P.tmpl;
+    const int len = T->len;
+    BestKey hit{P.max_mm + 1, 0, false};
+    for (int p = 0; p + len <= rd.n && !(hit.found && P.use_first); ++p) {
+        for (int s = 0; s < 2; ++s) {
+            if (s == 0 ? !P.fwd : !P.rev) continue;
+            int c = const_mismatches(T, s != 0, rd.p, p, P.max_mm);
+            if (c > P.max_mm) continue;
+            uint64_t cand;
+            int tot;
+            if (!combo_regions_candidate<W>(P, pools, rd, p, s != 0, c, cand, tot)) continue;
+            if (P.use_first) { hit.take(cand); break; }      // :197-217
+            hit.offer(cand, tot);
+        }
+    }
+    emit_key(cells, i, hit.found, hit.key);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -731,6 +826,78 @@ __global__ __launch_bounds__(STAGE_BLOCK, SCG_COMBO_WAVES) __attribute__((amdgpu
     }
     if (cells.unit_index) cells.unit_index[lane_read()] = hit.found ? hit.id[0] * P.n_pool[1] + hit.id[1] : -1;     // tally mode
     else emit_combo(cells, lane_read(), hit.found, hit.id[0], hit.id[1], P.n_pool[1]);
+}
+
+// Staged counterpart of combo_regions_candidate: the window's regions from the tile's planes, region r of the scanned
+// strand in pool `slot`.  nreg is uniform, so the loop is one body whatever the number of regions; the candidate is the
+// 64-bit key alone (an array of indices subscripted by `slot` would live in scratch).
+template<int NW, int NT, class W>
+__device__ __forceinline__ bool combo_regions_candidate_staged(const ScgComboRegionsParams& P, const ComboPools& pools, const Tile<NW>& tile, const StrandTable<NT>& st,
+                                                               const StagedRead& sr, int p, bool reverse, int c, uint64_t& key, int& total) {
+    const int nreg = P.nreg;
+    int obs = c;
+    uint64_t k = 0;
+#pragma unroll 1
+    for (int r = 0; r < nreg; ++r) {
+        const int slot = reverse ? (nreg - 1 - r) : r;
+        const int start = region_start<NT>(st, r, reverse);
+        const ScgIndex& tab = pools.index[slot];
+        QueryT<W> q = region_query<NW, W>(tile, sr.bit + p + start, tab.len, reverse);
+        int idx, d;
+        index_match<W>(tab, q, P.max_mm - obs, idx, d);
+        if (idx < 0) return false;
+        obs += d;
+        if (obs > P.max_mm) return false;
+        k += (uint64_t)(uint32_t)idx * pools.stride[slot];
+    }
+    key = k;
+    total = obs;
+    return true;
+}
+
+// combo_staged_kernel for nreg regions: the same tile, strand table, staging call, scan and candidate walk; the pools'
+// descriptors and strides in LDS (ComboPools: 896 bytes beside combo_staged_kernel's 208).  One instantiation per tile
+// shape and key width, whatever nreg is.  combo_regions_waves: the waves per SIMD asked of the compiler, the highest
+// per shape at which it reports no scratch (profiles/combo_regions_resource_usage.txt).
+template<int NW, int NT, int NC, class W>
+constexpr int combo_regions_waves() {
+#ifdef SCG_COMBO_REGIONS_WAVES       // (measurement builds: one bound for every shape)
+    return SCG_COMBO_REGIONS_WAVES;
+#else
+    return 8;
+#endif
+}
+
+template<int NW, int NT, int NC, class W>
+__global__ __launch_bounds__(STAGE_BLOCK, (combo_regions_waves<NW, NT, NC, W>())) __attribute__((amdgpu_num_sgpr(80))) void combo_regions_staged_kernel(ScgComboRegionsParams P, ScgReads R, int64_t n_reads,
+                                                                  ScgCounters cells, int32_t* __restrict__ error_flag) {
+    __shared__ Tile<NW> tile;
+    __shared__ StrandTable<NT> strands;
+    __shared__ ComboPools pools;
+    fill_strand_table<NT>(strands, P.scan);
+    load_combo_pools(pools, P);
+    StagedRead sr;
+    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, sr);      // (every lane reaches its barrier)
+    if (lane == Lane::idle) return;
+    if (lane == Lane::unstaged) { *error_flag = 1; return; }
+    BestKey hit{P.max_mm + 1, 0, false};
+    const ScgScan& T = P.scan;
+    uint32_t candF[NC], candR[NC];
+    scan_read<NW, NC>(tile, sr, T, P.fwd != 0, P.rev != 0, candF, candR);
+    const int last = last_position(sr.n, T.len);
+    for (;;) {
+        int p;
+        bool rev;
+        if (!next_candidate<NC>(candF, candR, last, p, rev)) break;
+        int c = window_mismatches<NW, NT>(tile, sr.bit + p, strands, rev);
+        if (c > P.max_mm) continue;
+        uint64_t cand;
+        int tot;
+        if (!combo_regions_candidate_staged<NW, NT, W>(P, pools, tile, strands, sr, p, rev, c, cand, tot)) continue;
+        if (P.use_first) { hit.take(cand); break; }
+        hit.offer(cand, tot);
+    }
+    emit_key(cells, lane_read(), hit.found, hit.key);
 }
 
 // Staged counterpart of mate_search.
@@ -1215,6 +1382,16 @@ template<int NW, int NT> struct LaunchCombo {
         return hipGetLastError();
     }
 };
+template<int NW, int NT> struct LaunchComboRegions {
+    static hipError_t go(const ScgComboRegionsParams& P, const ScgReads& R, int64_t n, const ScgCounters& cells, int32_t* flag, hipStream_t stream) {
+        const bool wide = P.index[0].wide != 0;          // a pool of 33..64 bases (every index is then built wide)
+        with_shape<NW>(compact_fits<NW>(P.scan.compact_ok, R.max_len, P.scan.len), wide, [&](auto s) {
+            using S = decltype(s);
+            hipLaunchKernelGGL((combo_regions_staged_kernel<NW, NT, S::NC, typename S::W>), dim3(staged_grid(n)), dim3(STAGE_BLOCK), extra_lds(), stream, P, R, n, cells, flag);
+        });
+        return hipGetLastError();
+    }
+};
 // Expected number of windows of a random read that pass a template's constant bases: with few, the pair search keeps
 // one hit per mate (dual_passes_kernel); a template that is found all over the place keeps both mates' tiles resident.
 static double expected_chance_hits(const ScgScan& T, int max_mm, int read_len) {
@@ -1329,6 +1506,18 @@ hipError_t launch_combo(const ScgComboParams& P, int tmpl_len, const ScgReads& R
         return hipGetLastError();
     }
     return dispatch_shape<LaunchCombo>(R.max_len, tmpl_len, P, R, n, cells, flag, stream);
+}
+
+// Combinations over P.nreg regions: the batches launch_combo gives each of its engines, by the pools' common key class.
+hipError_t launch_combo_regions(const ScgComboRegionsParams& P, int tmpl_len, const ScgReads& R, int64_t n, const ScgCounters& cells, int32_t* flag, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    if (use_general(R.max_len) || P.index[0].wide == 2) {
+        with_key(P.index[0].wide, [&](auto s) {
+            hipLaunchKernelGGL((combo_regions_kernel<typename decltype(s)::W>), dim3(grid_for(n)), dim3(BLOCK), 0, stream, P, R, n, cells);
+        });
+        return hipGetLastError();
+    }
+    return dispatch_shape<LaunchComboRegions>(R.max_len, tmpl_len, P, R, n, cells, flag, stream);
 }
 
 hipError_t launch_dual(const ScgDualParams& P, int tmpl_len, const ScgReads& R1, const ScgReads& R2, int64_t n, const ScgCounters& counts, int32_t* flag, hipStream_t stream) {

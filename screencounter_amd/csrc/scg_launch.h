@@ -23,6 +23,9 @@ hipError_t launch_single_paired(const ScgSingleParams& P, int tmpl_len, const Sc
 // countRandomBarcodes: d_hits[i] = (position << 1) | reverse of read i's template hit, or -1
 hipError_t launch_random(const ScgSingleParams& P, int tmpl_len, const ScgReads& R, int64_t n, int32_t* d_hits, int32_t* flag, hipStream_t stream);
 hipError_t launch_combo(const ScgComboParams& P, int tmpl_len, const ScgReads& R, int64_t n, const ScgCounters& cells, int32_t* flag, hipStream_t stream);
+// combinations over P.nreg variable regions: cell / key of read i = its mixed-radix key (ScgComboRegionsParams); `cells` counts
+// with atomics or carries a key stream (unit_pair), no index stream
+hipError_t launch_combo_regions(const ScgComboRegionsParams& P, int tmpl_len, const ScgReads& R, int64_t n, const ScgCounters& cells, int32_t* flag, hipStream_t stream);
 hipError_t launch_dual(const ScgDualParams& P, int tmpl_len, const ScgReads& R1, const ScgReads& R2, int64_t n, const ScgCounters& counts, int32_t* flag, hipStream_t stream);
 hipError_t launch_fold(int32_t* replicas, int replica_shift, int64_t n, int32_t* counters, hipStream_t stream);
 // hot[2][SCG_HOT_SLOTS] -> pair_of_counters[0], [1] (and clears the slots); ScgCounters::hot

@@ -11,6 +11,7 @@ using scg::key_class;
 
 // Big keys have the byte-wise general kernels only, whatever scg::staged_takes says of the batch.
 bool general_only(const scg_plan* P) {
+    if (P->kind == scg_plan::COMBO_REGIONS) return P->rtab[0].view.wide == 2;      // (all pools share one key class)
     return P->tab[0].view.wide == 2 || (P->kind == scg_plan::DUAL_SE_DIAG && P->tab_combined.view.wide == 2);
 }
 
@@ -194,6 +195,61 @@ std::unique_ptr<scg_plan> compile_combo(const char* constant, int strand,
     return P;
 }
 
+// Combinations over n_regions variable regions: kaori::CombinatorialBarcodesSingleEnd<max_size, n_regions>, whose
+// constructor, find_match, tie rule and sort are written for any number of regions (the reference's R glue instantiates
+// two: src/count_combo_barcodes_single.cpp:44-46).  The constructor's checks in its order
+// (CombinatorialBarcodesSingleEnd.hpp:79-93); what this engine cannot represent is SCG_ERR_UNSUPPORTED.
+std::unique_ptr<scg_plan> compile_combo_regions(const char* constant, int strand, const char* const* const* pools, const int32_t* n_pools,
+                                                int32_t n_regions, int mismatches, int use_first) {
+    if (!constant || (n_regions > 0 && (!pools || !n_pools))) throw Error(SCG_ERR_INVALID, "null argument");
+    if (n_regions < 1 || n_regions > SCG_MAX_REGIONS) {           // (the template argument: nothing to construct outside it)
+        throw Error(SCG_ERR_UNSUPPORTED, "this engine counts combinations of 1 to " + std::to_string(SCG_MAX_REGIONS) + " variable regions (got " +
+                    std::to_string(n_regions) + ")");
+    }
+    std::unique_ptr<scg_plan> P(new scg_plan);
+    P->kind = scg_plan::COMBO_REGIONS;
+    std::vector<int> plen(n_regions);
+    for (int r = 0; r < n_regions; ++r) {
+        if (n_pools[r] < 0 || (n_pools[r] > 0 && !pools[r])) throw Error(SCG_ERR_INVALID, "null argument");
+        plen[r] = scg::pool_length(pools[r], n_pools[r]);         // src/utils.cpp:15-17 (format_pointers per pool)
+    }
+    P->ht1 = scg::parse_template(constant, strand);
+    const ScgTemplate& t = P->ht1.t;
+    if (t.nreg != n_regions) {                                    // :79-81
+        throw Error(SCG_ERR_INVALID, "expected " + std::to_string(n_regions) + " variable regions in the constant template");
+    }
+    for (int r = 0; r < n_regions; ++r) check_region_length(t, r, plen[r]);      // :86-93
+    if (mismatches < 0) throw Error(SCG_ERR_INVALID, "negative number of mismatches");
+    // a combination is one 64-bit key, ~0 being "none" in a key stream: the pools' sizes must multiply to less than 2^63
+    uint64_t cells = 1;
+    for (int r = 0; r < n_regions; ++r) {
+        uint64_t next = 0;
+        if (__builtin_mul_overflow(cells, static_cast<uint64_t>(n_pools[r]), &next) || next >= (uint64_t(1) << 63)) {
+            throw Error(SCG_ERR_UNSUPPORTED, "the pools of the " + std::to_string(n_regions) + " variable regions span 2^63 combinations or more: beyond the 64-bit keys of this engine");
+        }
+        cells = next;
+    }
+    // one key width per kernel: every pool in the widest key class among them
+    int cls = 0;
+    for (int r = 0; r < n_regions; ++r) cls = std::max(cls, key_class(plen[r]));
+    P->n_regions = n_regions;
+    P->hpools.resize(static_cast<size_t>(n_regions));
+    P->pool_sizes.assign(n_pools, n_pools + n_regions);
+    for (int r = 0; r < n_regions; ++r) P->hpools[static_cast<size_t>(r)] = scg::build_index(pools[r], n_pools[r], plen[r], mismatches, cls);
+    uint64_t stride = 1;
+    for (int r = n_regions - 1; r >= 0; --r) {                    // (an empty pool: nothing is ever found, the strides do not matter)
+        P->stride[r] = stride;
+        stride *= static_cast<uint64_t>(std::max<int32_t>(n_pools[r], 1));
+    }
+    P->scan1 = scg::build_scan(t, mismatches);
+    P->n_pool[0] = P->n_pool[1] = 0;
+    P->sparse = cells > static_cast<uint64_t>(std::max<int64_t>(dense_cells(), 0));      // as compile_combo: $SCG_DENSE_CELLS switches it per call
+    P->n_counters = P->sparse ? 0 : static_cast<int64_t>(cells);
+    P->max_mm1 = mismatches;
+    P->use_first = use_first != 0;
+    return P;
+}
+
 std::unique_ptr<scg_plan> compile_dual(const char* constant1, int reverse1, int mismatches1, const char* const* pool1,
                                        const char* constant2, int reverse2, int mismatches2, const char* const* pool2,
                                        int32_t n_pool, int randomized, int use_first, int diagnostics) {
@@ -322,6 +378,18 @@ ScgComboParams combo_params(const scg_plan* P) {
     cp.tmpl = P->d_tmpl1.as<ScgTemplate>();
     cp.index[0] = P->tab[0].view; cp.index[1] = P->tab[1].view;
     cp.n_pool[0] = P->n_pool[0]; cp.n_pool[1] = P->n_pool[1];
+    cp.max_mm = P->max_mm1; cp.use_first = P->use_first;
+    cp.fwd = P->ht1.fwd; cp.rev = P->ht1.rev;
+    return cp;
+}
+
+// The combination search over the plan's n_regions pools (COMBO_REGIONS).
+ScgComboRegionsParams combo_regions_params(const scg_plan* P) {
+    ScgComboRegionsParams cp = ScgComboRegionsParams();
+    cp.scan = P->scan1;
+    cp.tmpl = P->d_tmpl1.as<ScgTemplate>();
+    cp.nreg = P->n_regions;
+    for (int r = 0; r < P->n_regions; ++r) { cp.index[r] = P->rtab[r].view; cp.stride[r] = P->stride[r]; }
     cp.max_mm = P->max_mm1; cp.use_first = P->use_first;
     cp.fwd = P->ht1.fwd; cp.rev = P->ht1.rev;
     return cp;
@@ -769,11 +837,13 @@ void launch_batch(scg_plan* P, const ScgReads& R, int64_t n, hipStream_t stream)
     if (P->kind == scg_plan::DUAL_SE_DIAG) { launch_batch_se_diag(P, R, n, stream); return; }
     scg_plan::Timer timer(P, stream);
     ScgCounters counts = plan_counters(P);
-    const bool tally = !P->sparse && use_tally(P, n) && scg::staged_takes(R.max_len) && !general_only(P);
+    const bool tally = !P->sparse && P->kind != scg_plan::COMBO_REGIONS && use_tally(P, n) && scg::staged_takes(R.max_len) && !general_only(P);
     if (P->sparse) counts.unit_pair = begin_pairs(P, stream, n);
     else if (tally) counts.unit_index = index_stream(P, stream, n);
     if (P->kind == scg_plan::SINGLE) {
         HIP_CHECK(scg::launch_single(single_params(P, P->tab[0].view), P->ht1.t.len, R, n, counts, P->error_flag.as<int32_t>(), stream));
+    } else if (P->kind == scg_plan::COMBO_REGIONS) {       // (cells or a key stream; its kernels write no index stream)
+        HIP_CHECK(scg::launch_combo_regions(combo_regions_params(P), P->ht1.t.len, R, n, counts, P->error_flag.as<int32_t>(), stream));
     } else {
         HIP_CHECK(scg::launch_combo(combo_params(P), P->ht1.t.len, R, n, counts, P->error_flag.as<int32_t>(), stream));
     }

@@ -117,6 +117,8 @@ std::unique_ptr<scg_plan> clone_compiled(const scg_plan& a) {
     b->rev1 = a.rev1; b->rev2 = a.rev2; b->randomized = a.randomized; b->use_first = a.use_first;
     b->diagnostics = a.diagnostics;
     b->first1 = a.first1; b->first2 = a.first2;
+    b->n_regions = a.n_regions; b->hpools = a.hpools; b->pool_sizes = a.pool_sizes;
+    std::copy(a.stride, a.stride + SCG_MAX_REGIONS, b->stride);
     b->n_counters = a.n_counters;
     b->sparse = a.sparse;
     if (a.rnd) {                                            // (the tally's settings; its table is made by random_to_device)
@@ -325,6 +327,7 @@ void result_counts(const std::vector<scg_plan*>& plans, int32_t* counts_out, int
 
 void result_combinations(const std::vector<scg_plan*>& plans, int32_t** idx_out, int32_t** freq_out, int64_t* k_out, int32_t* total_out) {
     const scg_plan* P = plans[0];
+    if (P->kind == scg_plan::COMBO_REGIONS) { result_combinations_regions(plans, idx_out, freq_out, k_out, total_out); return; }
     std::vector<int32_t> cells(static_cast<size_t>(P->n_counters) + 1);
     read_plans(plans, cells.data());
     const int32_t total = total_out ? narrow_total(total_of(plans)) : 0;      // (before anything is allocated for the caller)
@@ -502,6 +505,62 @@ void combo_list_of_plan(scg_plan* P, ComboList& out) {
         out.keys[j] = rows[j].first;
         out.counts[j] = static_cast<int32_t>(rows[j].second);
     }
+}
+
+void result_combinations_regions(const std::vector<scg_plan*>& plans, int32_t** idx_out, int32_t** freq_out, int64_t* k_out, int32_t* total_out) {
+    const scg_plan* P0 = plans[0];
+    const size_t nreg = static_cast<size_t>(P0->n_regions);
+    std::vector<std::pair<uint64_t, int64_t> > rows;             // (mixed-radix key, count), ascending
+    for (scg_plan* p : plans) {                                   // (the oversize-read flag, as before every read-out)
+        DeviceGuard g(p->device);
+        read_counters(p, nullptr);
+    }
+    if (P0->sparse) {
+        const std::unordered_map<uint64_t, int64_t> m = sparse_merged(plans);
+        rows.assign(m.begin(), m.end());
+        std::sort(rows.begin(), rows.end());
+    } else if (P0->n_counters > 0) {
+        // the flat histogram as (all pools but the last) x (last pool): cell = head * n_last + last
+        const int64_t n_last = P0->pool_sizes[nreg - 1], n_head = P0->n_counters / n_last;
+        if (n_head > static_cast<int64_t>(INT32_MAX)) {
+            throw Error(SCG_ERR_UNSUPPORTED, "a dense grid of " + std::to_string(n_head) + " x " + std::to_string(n_last) + " cells is beyond the device compaction");
+        }
+        for (scg_plan* p : plans) {
+            DeviceGuard g(p->device);
+            ComboList list;
+            compact_cells_on_device(p->counters, static_cast<int32_t>(n_head), static_cast<int32_t>(n_last), list);
+            const size_t before = rows.size();
+            for (size_t j = 0; j < list.keys.size(); ++j) {
+                rows.push_back(std::make_pair((list.keys[j] >> 32) * static_cast<uint64_t>(n_last) + (list.keys[j] & 0xFFFFFFFFu), static_cast<int64_t>(list.counts[j])));
+            }
+            if (before) {                                         // several devices: equal keys of two sorted lists share a row
+                std::inplace_merge(rows.begin(), rows.begin() + static_cast<long>(before), rows.end());
+                size_t w = 0;
+                for (size_t j = 0; j < rows.size(); ++j) {
+                    if (w && rows[w - 1].first == rows[j].first) rows[w - 1].second += rows[j].second;
+                    else rows[w++] = rows[j];
+                }
+                rows.resize(w);
+            }
+        }
+    }
+    const int32_t total = total_out ? narrow_total(total_of(plans)) : 0;      // (before anything is allocated for the caller)
+    const size_t k = rows.size();
+    OutPair<int32_t, int32_t> out(nreg * k + 1, k + 1);
+    for (size_t j = 0; j < k; ++j) {
+        if (rows[j].second > static_cast<int64_t>(INT32_MAX)) throw Error(SCG_ERR_INVALID, "a count exceeds the 32-bit range of the count vectors");
+        uint64_t key = rows[j].first;
+        for (size_t r = nreg; r-- > 0;) {
+            const uint64_t size = static_cast<uint64_t>(P0->pool_sizes[r]);
+            if (size == 0 || (r == 0 && key >= size)) throw Error(SCG_ERR_DEVICE, "internal: combination out of range");
+            out.a[nreg * j + r] = static_cast<int32_t>(key % size);
+            key /= size;
+        }
+        out.b[j] = static_cast<int32_t>(rows[j].second);
+    }
+    out.release(idx_out, freq_out);
+    *k_out = static_cast<int64_t>(k);
+    if (total_out) *total_out = total;
 }
 
 void combo_list_of_outputs(const int32_t* idx, const int32_t* freq, int64_t k, ComboList& out) {

@@ -124,6 +124,15 @@ class Plan:
                                            int(bool(use_first))), "combo", (len(pool0), len(pool1)), device)
 
     @classmethod
+    def combo_regions(cls, template: str, strand: int, pools: Sequence[Sequence[str]], mismatches: int = 0,
+                      use_first: bool = True, device: int = -1) -> "Plan":
+        """Combinations over len(pools) variable regions (kaori::CombinatorialBarcodesSingleEnd for any number of regions,
+        1 to 8 here): pools[r] for region r of the forward template.  Counted with count(), read with read_combinations()."""
+        rows, sizes, _keep = _lib.cstr_matrix(pools)
+        return cls._new("scg_plan_combo_regions", (template.encode(), int(strand), rows, sizes, len(pools), int(mismatches),
+                                                   int(bool(use_first))), "combo_regions", tuple(len(p) for p in pools), device)
+
+    @classmethod
     def dual(cls, template1: str, reverse1: bool, mismatches1: int, pool1: Sequence[str],
              template2: str, reverse2: bool, mismatches2: int, pool2: Sequence[str],
              randomized: bool = False, use_first: bool = True, device: int = -1, diagnostics: bool = False) -> "Plan":
@@ -280,6 +289,20 @@ class Plan:
         total = C.c_int64(0)
         err = errbuf()
         with combo_outputs(self._lib) as (combos, take):
+            check(self._lib.scg_plan_read_combinations(self._h, *combos, C.byref(total), C.c_void_p(_stream_handle(stream)),
+                                                       err, _lib.ERRCAP), err)
+            idx, freq = take()
+        return idx, freq, int(total.value)
+
+    def read_combinations(self, stream=None):
+        """Plans of Plan.combo_regions: (indices int32[n_regions, K] sorted by (first, ..., last), freq int32[K], total).
+        Plans of Plan.combo: read_combo()'s result, n_regions being 2."""
+        if self.kind not in ("combo", "combo_regions"):
+            raise ValueError("read_combinations needs a combination plan")
+        rows = int(self._lib.scg_plan_num_regions(self._h))
+        total = C.c_int64(0)
+        err = errbuf()
+        with combo_outputs(self._lib, rows) as (combos, take):
             check(self._lib.scg_plan_read_combinations(self._h, *combos, C.byref(total), C.c_void_p(_stream_handle(stream)),
                                                        err, _lib.ERRCAP), err)
             idx, freq = take()

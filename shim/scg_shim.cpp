@@ -26,9 +26,9 @@ void check(int rc, const char* err) { if (rc != SCG_OK) Rcpp::stop(err); }
 
 // Combinations as libscg hands them out (malloc'd: 2 x K indices, column-major and 0-based, sorted by (first, second); K
 // frequencies) -> what R gets.
-Rcpp::IntegerMatrix combination_indices(const int32_t* idx, int64_t k) {
-    Rcpp::IntegerMatrix m(2, k);
-    std::copy(idx, idx + 2 * k, m.begin());
+Rcpp::IntegerMatrix combination_indices(const int32_t* idx, int64_t k, int rows = 2) {     // (rows: the variable regions, where not 2)
+    Rcpp::IntegerMatrix m(rows, k);
+    std::copy(idx, idx + rows * k, m.begin());
     return m;
 }
 Rcpp::IntegerVector combination_counts(const int32_t* freq, int64_t k) { return Rcpp::IntegerVector(freq, freq + k); }
@@ -467,4 +467,36 @@ Rcpp::List combine_combinations(Rcpp::IntegerVector first, Rcpp::IntegerVector s
     check(scg_combine_combinations(idx.data(), freq.data(), k.data(), (int32_t)n_files,
                                    &found.idx, &found.k, &found.col_ptr, &found.rows, &found.freq, err, sizeof(err)), err);
     return Rcpp::List::create(found.indices(), found.counts(n_files));
+}
+
+// Combinations over any number of variable regions (kaori::CombinatorialBarcodesSingleEnd<N, V> for V = length(pool), 1 to
+// 8): count_combo_barcodes_single's arguments and result shape, the matrix of indices having one row per region.
+//[[Rcpp::export(rng=false)]]
+Rcpp::List count_combo_barcodes_regions(std::string path, std::string constant, int strand, Rcpp::List pool,
+                                        int mismatches, bool use_first, int nthreads) {
+    PoolRows pools(pool);
+    Combinations found; int total = 0;
+    char err[1024];
+    check(scg_count_combo_barcodes_regions(path.c_str(), constant.c_str(), strand, pools.rows.data(), pools.sizes.data(), (int32_t)pools.rows.size(),
+                                           mismatches, use_first, nthreads, &found.idx, &found.freq, &found.k, &total, err, sizeof(err)), err);
+    return Rcpp::List::create(combination_indices(found.idx, found.k, (int)pools.rows.size()), found.counts(), Rcpp::IntegerVector::create(total));
+}
+
+//[[Rcpp::export(rng=false)]]
+Rcpp::List count_combo_barcodes_regions_files(Rcpp::CharacterVector paths, std::string constant, int strand, Rcpp::List pool,
+                                              int mismatches, bool use_first, int nthreads) {
+    PoolRows pools(pool);
+    auto f = borrow(paths);
+    PerFileCombinations found(f.size());
+    Rcpp::IntegerVector totals(paths.size());
+    char err[1024];
+    check(scg_count_combo_barcodes_regions_files(f.data(), (int32_t)f.size(), constant.c_str(), strand, pools.rows.data(), pools.sizes.data(),
+                                                 (int32_t)pools.rows.size(), mismatches, use_first, nthreads,
+                                                 found.idx.data(), found.freq.data(), found.k.data(), totals.begin(), err, sizeof(err)), err);
+    Rcpp::List out(paths.size());                        // one count_combo_barcodes_regions() result per file
+    for (R_xlen_t i = 0; i < paths.size(); ++i) {
+        out[i] = Rcpp::List::create(combination_indices(found.idx[i], found.k[i], (int)pools.rows.size()), found.counts(i),
+                                    Rcpp::IntegerVector::create(totals[i]));
+    }
+    return out;
 }

@@ -13,6 +13,7 @@ import numpy as np  # noqa: E402
 import screencounter_amd as sc  # noqa: E402
 from oracle.pyoracle import Oracle, OracleError, write_fastq  # noqa: E402
 from tests import gen  # noqa: E402
+from tests import combo_regions_ref  # noqa: E402
 from tests import single_paired_ref  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
@@ -53,6 +54,27 @@ def one(kind, rng, tmp):
             p.count(s, o)
             got = p.read_combo()
         assert got[2] == exp[2] and same(got[0], exp[0]) and same(got[1], exp[1]), c
+    elif kind == "combo_regions":          # 1 to 8 regions, against the restatement (tests/combo_regions_ref.py), plan and file entry
+        V = rng.choice([1, 2, 3, 4, 5, 8])
+        lens = [rng.choice([3, 4, 6, 9, 14] if V > 3 else [3, 6, 14, 33, 40, 70]) for _ in range(V)]
+        c = combo_regions_ref.make_case(rng, lens, [rng.choice([1, 3, 8, 30]) for _ in range(V)], rng.choice([1, 30, 200]), rng.choice([0, 1, 2]),
+                                        rng.choice([0, 1, 2, 3]), alphabet=rng.choice(["AC", gen.BASES]), iupac=rng.choice([0, 0, 0.05]),
+                                        begins=rng.random() < 0.2, ends=rng.random() < 0.2, p_sub=rng.choice([0, 0.03, 0.08]),
+                                        p_lower=rng.choice([0, 0.3]), pad_hi=rng.choice([0, 5, 30]))
+        args = (c["template"], c["strand"], c["pools"], c["mismatches"], rng.random() < 0.5)
+        os.environ["SCG_DENSE_CELLS"] = rng.choice(["0", str(1 << 26)])
+        try:
+            exp = combo_regions_ref.count_combo_regions(ora, c["reads"], *args)
+            s, o = sc.upload_reads(c["reads"], dev)
+            with sc.Plan.combo_regions(*args) as p:
+                p.count(s, o)
+                got = p.read_combinations()
+            fq = os.path.join(tmp, "c.fastq")
+            write_fastq(fq, c["reads"])
+            for g in (got, sc.count_combo_barcodes_regions(fq, *args)):
+                assert g[2] == exp[2] and same(g[0], exp[0]) and same(g[1], exp[1]), c
+        finally:
+            del os.environ["SCG_DENSE_CELLS"]
     elif kind in ("dual", "dual_diag", "paired_combo"):
         c = gen.random_paired_combo_case(rng) if kind == "paired_combo" else gen.random_dual_case(rng, hazard_free=True, max_mm=2)
         s1, o1 = sc.upload_reads(c["reads1"], dev)
@@ -99,7 +121,7 @@ def one(kind, rng, tmp):
         assert same(got[0], exp[0]) and same(got[1], exp[1]), c
 
 
-kinds = ["single", "single_paired", "combo", "dual", "dual_diag", "paired_combo", "dual_se", "dual_se_diag", "random", "match"]
+kinds = ["single", "single_paired", "combo", "combo_regions", "dual", "dual_diag", "paired_combo", "dual_se", "dual_se_diag", "random", "match"]
 t0 = last = time.time()
 it = 0
 with tempfile.TemporaryDirectory() as tmp:
