@@ -593,6 +593,9 @@ __global__ __launch_bounds__(BLOCK) void dual_kernel(ScgDualParams P, ScgReads R
 // =============================================================================================
 // Staged kernels
 // =============================================================================================
+// amdgpu_num_sgpr(80) on the staged kernels: what the compiler itself allows at 8 wavefronts per SIMD on gfx950 (800 / 8
+// less the 16 it keeps for the trap handler, in granules of 16).  Asking for 96 changes nothing in the kernels launched
+// with a bound of 8 -- they stay at 78 -- so the attribute only holds the shapes with a lower bound to the same budget.
 // W = uint32_t: one variable region of <= 32 bases (the hot configuration).  W = uint64_t: keys of up to
 // 64 bases, one region or several concatenated (wide barcodes, countDualBarcodesSingleEnd).
 template<int NW, int NT, int NC, class W, class Hit = BestSingle>
@@ -639,9 +642,8 @@ __global__ __launch_bounds__(STAGE_BLOCK, SCG_SINGLE_WAVES) __attribute__((amdgp
                                                                    ScgCounters counts, int32_t* __restrict__ error_flag) {
     __shared__ Tile<NW> tile;
     __shared__ StrandTable<NT> strands;
-    fill_strand_table<NT>(strands, P.scan);
     StagedRead sr;
-    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, sr);
+    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, strands, sr);
     if (lane == Lane::idle) return;
     if (lane == Lane::unstaged) { *error_flag = 1; return; }
     int idx;
@@ -680,9 +682,8 @@ __global__ __launch_bounds__(STAGE_BLOCK, (assign_waves<NW, NT, NC, W>())) __att
                                                                    ScgAssignOut out, int32_t* __restrict__ error_flag) {
     __shared__ Tile<NW> tile;
     __shared__ StrandTable<NT> strands;
-    fill_strand_table<NT>(strands, P.scan);
     StagedRead sr;
-    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, sr);
+    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, strands, sr);
     if (lane == Lane::idle) return;
     if (lane == Lane::unstaged) {
         *error_flag = 1;
@@ -739,9 +740,8 @@ __global__ __launch_bounds__(STAGE_BLOCK) __attribute__((amdgpu_num_sgpr(80))) v
                                                                    int32_t* __restrict__ hits, int32_t* __restrict__ error_flag) {
     __shared__ Tile<NW> tile;
     __shared__ StrandTable<NT> strands;
-    fill_strand_table<NT>(strands, P.scan);
     StagedRead sr;
-    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, sr);
+    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, strands, sr);
     if (lane == Lane::idle) return;
     if (lane == Lane::unstaged) { *error_flag = 1; return; }
     uint32_t candF[NC], candR[NC];
@@ -796,14 +796,11 @@ __global__ __launch_bounds__(STAGE_BLOCK, SCG_COMBO_WAVES) __attribute__((amdgpu
     __shared__ Tile<NW> tile;
     __shared__ StrandTable<NT> strands;
     __shared__ ScgIndex pools[SCG_COMBO_REGIONS];
-    fill_strand_table<NT>(strands, P.scan);
-    if (threadIdx.x < SCG_COMBO_REGIONS * (sizeof(ScgIndex) / 4)) {
-        static_assert(sizeof(ScgIndex) % 4 == 0, "copied by dwords");
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(&P.index[0]);
-        reinterpret_cast<uint32_t*>(&pools[0])[threadIdx.x] = src[threadIdx.x];
-    }
+    static_assert(sizeof(ScgIndex) % 4 == 0, "copied by dwords");
     StagedRead sr;
-    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, sr);
+    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, strands, sr, [&]() {
+        fill_from_arguments(reinterpret_cast<uint32_t*>(&pools[0]), &P.index[0], SCG_COMBO_REGIONS * (sizeof(ScgIndex) / 4));
+    });
     if (lane == Lane::idle) return;
     if (lane == Lane::unstaged) { *error_flag = 1; return; }
     BestCombo hit{P.max_mm + 1, {0, 0}, false};
@@ -874,10 +871,8 @@ __global__ __launch_bounds__(STAGE_BLOCK, (combo_regions_waves<NW, NT, NC, W>())
     __shared__ Tile<NW> tile;
     __shared__ StrandTable<NT> strands;
     __shared__ ComboPools pools;
-    fill_strand_table<NT>(strands, P.scan);
-    load_combo_pools(pools, P);
     StagedRead sr;
-    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, sr);      // (every lane reaches its barrier)
+    const Lane lane = stage_tile<NW, NT>(P.scan, R, n_reads, tile, strands, sr, [&]() { load_combo_pools(pools, P); });      // (every lane reaches its barrier)
     if (lane == Lane::idle) return;
     if (lane == Lane::unstaged) { *error_flag = 1; return; }
     BestKey hit{P.max_mm + 1, 0, false};

@@ -26,6 +26,7 @@
 #define SCG_STAGED_HIP_H
 
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <type_traits>
 #include "scg_engine.hip.h"
 
@@ -57,8 +58,9 @@ struct Tile {
 // gathered with v_dot4_u32_u8 against power-of-two weights, straight from ASCII bits 1 and 2 (so
 // scaled by 2 and 4).  When every lane of the wavefront holds only standard bases -- the rule in
 // real data, where N calls are rare -- the validity plane is all ones and its gather (a second byte
-// permute per dword plus a third dot product) is skipped.
-__device__ __forceinline__ void transpose_chunk(const uint4& x, uint32_t& p0, uint32_t& p1, uint32_t& v) {
+// permute per dword plus a third dot product) is skipped.  `live`: false in a lane whose chunk is a stand-in (a clamped
+// load of stage_reads) and whose planes nobody stores: it has no say in that.
+__device__ __forceinline__ void transpose_chunk(const uint4& x, uint32_t& p0, uint32_t& p1, uint32_t& v, bool live = true) {
     const uint32_t d[4] = {x.x, x.y, x.z, x.w};
     uint32_t a0[2] = {0, 0}, a1[2] = {0, 0};
     uint32_t z[4];
@@ -74,7 +76,7 @@ __device__ __forceinline__ void transpose_chunk(const uint4& x, uint32_t& p0, ui
     }
     p0 = (a0[0] >> 1) | (a0[1] << 7);
     p1 = (a1[0] >> 2) | (a1[1] << 6);
-    if (__builtin_amdgcn_ballot_w64((z[0] | z[1] | z[2] | z[3]) != 0) == 0) {     // wave-uniform
+    if (__builtin_amdgcn_ballot_w64(live && (z[0] | z[1] | z[2] | z[3]) != 0) == 0) {     // wave-uniform
         v = 0xFFFFu;
     } else {
         // z has no bit in positions 1, 2 (the table byte repeats the code bits) or 5, so z + 0x0C stays inside its byte:
@@ -95,9 +97,15 @@ __device__ __forceinline__ void transpose_chunk(const uint4& x, uint32_t& p0, ui
 // Phase A.  Returns false when the workgroup's span does not fit the tile (caller falls back to
 // the byte-wise engine for the whole workgroup).  On success `span0` is the byte offset (from
 // R.seqs) that bit 0 of the planes corresponds to; it may be negative by up to 15.
-template<int NW>
+// `fill` is the caller's other work before the barrier that needs no read bytes (copies of kernel arguments into
+// LDS): it is called once on every path that returns true, behind the issue of the first round of loads, so that
+// nothing but the span arithmetic stands between a workgroup's start and its first requests to HBM.
+// ONE_TILE: the caller is stage_tile (one tile per workgroup, staged once).
+struct NoFill { __device__ __forceinline__ void operator()() const {} };
+
+template<int NW, bool ONE_TILE = false, class Fill = NoFill>
 __device__ __forceinline__ bool stage_reads(const ScgReads& R, int64_t n_reads, int64_t r0, int nr,
-                                            Tile<NW>& tile, int64_t& span0) {
+                                            Tile<NW>& tile, int64_t& span0, Fill&& fill = Fill()) {
     uint64_t b0, b1, total;
     if (R.offsets) {
         b0 = R.offsets[r0];
@@ -116,56 +124,139 @@ __device__ __forceinline__ bool stage_reads(const ScgReads& R, int64_t n_reads, 
     uint16_t* h0 = reinterpret_cast<uint16_t*>(tile.p0);
     uint16_t* h1 = reinterpret_cast<uint16_t*>(tile.p1);
     uint16_t* hv = reinterpret_cast<uint16_t*>(tile.v);
-    // All of a lane's loads are issued before any is consumed, so that it has 2*NW independent
-    // 16-byte requests in flight instead of one HBM round trip per chunk.  Only the first and the
-    // last workgroup of a buffer can touch bytes outside [0, total); they take the guarded loop.
+    // A lane has BATCH (= NW) independent 16-byte requests in flight, not one HBM round trip per chunk; a tile is two
+    // rounds of them, rarely three.  Only the first and the last workgroup of a buffer can touch bytes outside
+    // [0, total); they take the guarded byte loop (as does a span of no bytes at all).
 #ifdef SCG_STAGE_BATCH
     constexpr int BATCH = SCG_STAGE_BATCH;
 #else
     constexpr int BATCH = NW;
 #endif
-    const bool edge = span0 < 0 || (uint64_t)(span0 + 16 * (int64_t)nchunks) > total;
-    for (int c0 = threadIdx.x; c0 < nchunks; c0 += STAGE_BLOCK * BATCH) {
-        uint4 x[BATCH];
-        const uint8_t* base = R.seqs + span0 + 16 * (int64_t)c0;
-        if (!edge) {
+    constexpr int ROUND = STAGE_BLOCK * BATCH;      // chunks per round of the workgroup
+    const bool edge = nchunks == 0 || span0 < 0 || (uint64_t)(span0 + 16 * (int64_t)nchunks) > total;
+    uint4 x[BATCH];
+    auto store = [&](int c, uint32_t p0, uint32_t p1, uint32_t v) {
+        h0[c] = (uint16_t)p0;
+        h1[c] = (uint16_t)p1;
+        hv[c] = (uint16_t)v;
+    };
+    auto load_edge = [&](int c0) {
 #pragma unroll
-            for (int k = 0; k < BATCH; ++k) {
-                if (c0 + k * STAGE_BLOCK < nchunks) {      // (x[k] stays unread otherwise)
-                    // streamed once: non-temporal, so the read bytes do not evict the library index from L2
-                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                    u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(base + (size_t)k * STAGE_BLOCK * 16));
-                    x[k] = make_uint4(t.x, t.y, t.z, t.w);
+        for (int k = 0; k < BATCH; ++k) {       // static k: x[] must stay in registers
+            x[k] = make_uint4(0, 0, 0, 0);
+            const int c = c0 + k * STAGE_BLOCK;
+            if (c < nchunks) {
+                int64_t cb = span0 + 16 * (int64_t)c;
+                uint32_t t[4] = {0, 0, 0, 0};
+                for (int j = 0; j < 16; ++j) {
+                    int64_t o = cb + j;
+                    uint32_t byte = (o >= 0 && (uint64_t)o < total) ? R.seqs[o] : 0u;
+                    t[j >> 2] |= byte << (8 * (j & 3));
                 }
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < BATCH; ++k) {       // static k: x[] must stay in registers
-                x[k] = make_uint4(0, 0, 0, 0);
-                const int c = c0 + k * STAGE_BLOCK;
-                if (c < nchunks) {
-                    int64_t cb = span0 + 16 * (int64_t)c;
-                    uint32_t t[4] = {0, 0, 0, 0};
-                    for (int j = 0; j < 16; ++j) {
-                        int64_t o = cb + j;
-                        uint32_t byte = (o >= 0 && (uint64_t)o < total) ? R.seqs[o] : 0u;
-                        t[j >> 2] |= byte << (8 * (j & 3));
-                    }
-                    x[k] = make_uint4(t[0], t[1], t[2], t[3]);
-                }
+                x[k] = make_uint4(t[0], t[1], t[2], t[3]);
             }
         }
+    };
+    auto transpose_round = [&](int c0) {
 #pragma unroll
         for (int k = 0; k < BATCH; ++k) {
             const int c = c0 + k * STAGE_BLOCK;
             if (c < nchunks) {
                 uint32_t p0, p1, v;
                 transpose_chunk(x[k], p0, p1, v);
-                h0[c] = (uint16_t)p0;
-                h1[c] = (uint16_t)p1;
-                hv[c] = (uint16_t)v;
+                store(c, p0, p1, v);
             }
         }
+    };
+    if constexpr (!ONE_TILE) {
+        // The pair kernels stage inside their search loops, where the straight-line rounds below cost the randomized and
+        // the two-tile shapes a wavefront per SIMD (13-16 VGPRs): they keep their one loop, all of a round's loads issued
+        // before the first is consumed, guarded chunk by chunk, byte by byte in the first and last workgroup.
+        fill();
+        for (int c0 = threadIdx.x; c0 < nchunks; c0 += ROUND) {
+            const uint8_t* base = R.seqs + span0 + 16 * (int64_t)c0;
+            if (!edge) {
+#pragma unroll
+                for (int k = 0; k < BATCH; ++k) {
+                    if (c0 + k * STAGE_BLOCK < nchunks) {      // (x[k] stays unread otherwise)
+                        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                        u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(base + (size_t)k * STAGE_BLOCK * 16));
+                        x[k] = make_uint4(t.x, t.y, t.z, t.w);
+                    }
+                }
+            } else {
+                load_edge(c0);
+            }
+            transpose_round(c0);
+        }
+        return true;
+    }
+    if (edge) {
+        fill();
+        for (int c0 = threadIdx.x; c0 < nchunks; c0 += ROUND) {
+            load_edge(c0);
+            transpose_round(c0);
+        }
+        return true;
+    }
+    // Every chunk of the span lies inside the buffer here, so a load needs no guard of its own: a chunk index past the
+    // span's end is clamped to the last chunk (loaded for nothing, its planes never stored) and the BATCH loads of a
+    // round are straight-line code.  The transposes of chunk k then wait for load k alone (counted vmcnt waits), and
+    // load k of the next round goes out as soon as chunk k has left its registers, in front of its LDS stores.
+    const uint8_t* const first = R.seqs + span0;
+    const int last = nchunks - 1;
+    auto load = [&](int c) {
+        // streamed once: non-temporal, so the read bytes do not evict the library index from L2
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(first + 16 * (int64_t)(c < last ? c : last)));
+        return make_uint4(t.x, t.y, t.z, t.w);
+    };
+#pragma unroll
+    for (int k = 0; k < BATCH; ++k) x[k] = load((int)threadIdx.x + k * STAGE_BLOCK);
+    fill();
+    // The rounds are unrolled: as a loop, the compiler rotates x[] through copies at the back edge, which wait for every
+    // load.  Whether a next round exists is decided once per round, not per chunk: a branch between two chunks makes the
+    // compiler count the waits behind it for the path with fewer loads in flight, one load short per branch.  A tile holds
+    // MAXCHUNKS chunks at the most, so the third round is a single chunk per lane (`live`, static) and rare; it is loaded plainly.
+    constexpr int MAXCHUNKS = Tile<NW>::CAP_BYTES / 16, ROUNDS = (MAXCHUNKS + ROUND - 1) / ROUND;
+    auto live = [](int r, int k) { return r * ROUND + k * STAGE_BLOCK < MAXCHUNKS; };
+    auto round = [&](int r, bool pipelined) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < BATCH; ++k) {
+            if (!live(r, k)) continue;
+            const int c = r * ROUND + (int)threadIdx.x + k * STAGE_BLOCK;
+            uint32_t p0, p1, v;
+            transpose_chunk(x[k], p0, p1, v, c < nchunks);
+            if (pipelined && live(r + 1, k)) x[k] = load(c + ROUND);
+            if (c < nchunks) store(c, p0, p1, v);
+        }
+    };
+    // (Every path leaves on its own below, so that x[] is live across no join: where two paths that loaded x[] met, the
+    // compiler gave the loads other registers and copied them over, waiting for each.)
+    auto load_round = [&](int r) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < BATCH; ++k)
+            if (live(r, k)) x[k] = load(r * ROUND + (int)threadIdx.x + k * STAGE_BLOCK);
+    };
+    // The pipelined round holds two rounds' chunks in registers, 8 * BATCH VGPRs: the 160-base shapes have them, the
+    // 320-base shapes (BATCH = 10) would pay with a wavefront per SIMD and load their second round behind the first.
+    constexpr bool PIPELINED = BATCH <= 5;
+    if constexpr (PIPELINED) {
+        if (nchunks <= ROUND) {                                 // (wave-uniform, as every test of nchunks here)
+            round(0, false);
+            return true;
+        }
+        round(0, true);
+    } else {
+        round(0, false);
+        if (nchunks <= ROUND) return true;
+        load_round(1);
+    }
+#pragma unroll
+    for (int r = 1; r < ROUNDS; ++r) {
+        round(r, false);
+        if ((r + 1) * ROUND >= nchunks) return true;
+        load_round(r + 1);
     }
     return true;
 }
@@ -243,6 +334,12 @@ __device__ __forceinline__ void seed_candidates(const BasePlanes<NW>& E, const S
             // plane shifted to a seed base is one funnel shift per word straight from two adjacent words of E (no running
             // copy), and two bases are folded into g with a single 3-input AND.  The host pads every walk to an even step count.
             static_assert(NC + 2 <= NW, "compact scanner: candidate words + two plane words of look-ahead");
+            // The seed's four walks come in with ONE 64-byte scalar load and one wait, before the first funnel shift: read
+            // word by word behind the `left` tests, each used word was a scalar load and a wait of its own in the middle
+            // of the shifts, five or six dependent round trips a seed.
+            typedef uint32_t WalkWords __attribute__((ext_vector_type(SCG_SEED_STEPS), aligned(4)));
+            static_assert(sizeof(ScgSeed::walk) == 4 * SCG_SEED_STEPS, "walk[c].w[wi] is word c * SCG_SEED_STEPS / 4 + wi");
+            const WalkWords words = *reinterpret_cast<const WalkWords*>(&S.seed[s].walk[0].w[0]);
             auto walk = [&](auto blk_tag) {
                 constexpr int B = decltype(blk_tag)::value;
 #pragma unroll
@@ -251,7 +348,7 @@ __device__ __forceinline__ void seed_candidates(const BasePlanes<NW>& E, const S
 #pragma unroll
                     for (int wi = 0; wi < SCG_SEED_STEPS / 4; ++wi) {
                         if (left <= 0) break;
-                        const uint32_t word = S.seed[s].walk[c].w[wi];
+                        const uint32_t word = words[c * (SCG_SEED_STEPS / 4) + wi];
 #pragma unroll
                         for (int h = 0; h < 2; ++h) {
                             if (left <= 2 * h) break;
@@ -367,25 +464,44 @@ struct StrandTable {
     uint32_t w[2 * STRIDE];
 };
 
+// The wavefront that copies kernel arguments into LDS during phase A (the strand table, the combination kernels' pool
+// descriptors): the workgroup's last, which has the fewest chunks to transpose when the span does not divide evenly.
+constexpr int FILL_LANE0 = STAGE_BLOCK - (STAGE_BLOCK < 64 ? STAGE_BLOCK : 64);
+
+// `ndwords` of kernel arguments from `src` to LDS at `dst`, one dword per lane of the fill wavefront and round.  The
+// barrier that makes the copy visible is the caller's (stage_tile's).
+__device__ __forceinline__ void fill_from_arguments(uint32_t* dst, const void* src, int ndwords) {
+    for (int i = (int)threadIdx.x - FILL_LANE0; i >= 0 && i < ndwords; i += STAGE_BLOCK - FILL_LANE0)
+        dst[i] = reinterpret_cast<const uint32_t*>(src)[i];
+}
+
+// Every lane of the workgroup may call this; the fill wavefront does the work, each of its lanes one word of the table
+// (two in the 256-base shapes) taken from the kernel arguments by its own index -- not one lane's eleven serial stores
+// behind three dependent scalar loads.  The per-lane index makes it a vector load, and vector loads return in order: called
+// behind the staging loads (stage_reads), the fill wavefront waits for all of its first round before it stores the table
+// and gives up the counted waits of that round; the other three wavefronts of the workgroup keep them.
 template<int NT>
 __device__ __forceinline__ void fill_strand_table(StrandTable<NT>& st, const ScgScan& T) {
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            st.w[i] = T.fplane0[i];
-            st.w[NT + i] = T.fplane1[i];
-            st.w[2 * NT + i] = T.fmask[i];
-            st.w[StrandTable<NT>::STRIDE + i] = T.rplane0[i];
-            st.w[StrandTable<NT>::STRIDE + NT + i] = T.rplane1[i];
-            st.w[StrandTable<NT>::STRIDE + 2 * NT + i] = T.rmask[i];
+    constexpr int STRIDE = StrandTable<NT>::STRIDE, W = SCG_MAX_TEMPLATE / 32, R = SCG_MAX_REGIONS;
+    // the six planes lie behind one another in ScgScan, strand-major, and so do the four region arrays, kind-major
+    static_assert(offsetof(ScgScan, fplane1) - offsetof(ScgScan, fplane0) == 4 * W && offsetof(ScgScan, fmask) - offsetof(ScgScan, fplane0) == 8 * W &&
+                  offsetof(ScgScan, rplane0) - offsetof(ScgScan, fplane0) == 12 * W && offsetof(ScgScan, rplane1) - offsetof(ScgScan, fplane0) == 16 * W &&
+                  offsetof(ScgScan, rmask) - offsetof(ScgScan, fplane0) == 20 * W, "plane (strand, kind, word) at fplane0 + (3 strand + kind) W + word");
+    static_assert(offsetof(ScgScan, rstart) - offsetof(ScgScan, fstart) == 4 * R && offsetof(ScgScan, flen) - offsetof(ScgScan, fstart) == 8 * R &&
+                  offsetof(ScgScan, rlen) - offsetof(ScgScan, fstart) == 12 * R, "region (kind, strand, r) at fstart + (2 kind + strand) R + r");
+    const uint32_t* scan = reinterpret_cast<const uint32_t*>(&T);      // (the whole ScgScan as dwords: the indices below cross its arrays)
+    const uint32_t* planes = scan + offsetof(ScgScan, fplane0) / 4;
+    const uint32_t* regions = scan + offsetof(ScgScan, fstart) / 4;
+    for (int i = (int)threadIdx.x - FILL_LANE0; i >= 0 && i < 2 * STRIDE; i += STAGE_BLOCK - FILL_LANE0) {
+        const int strand = i >= STRIDE, col = i - strand * STRIDE;
+        uint32_t word;
+        if (col < 3 * NT) {
+            word = planes[(3 * strand + col / NT) * W + col % NT];
+        } else {
+            const int k = col - 3 * NT;                       // region starts, then region lengths
+            word = regions[(2 * (k / R) + strand) * R + k % R];
         }
-#pragma unroll
-        for (int r = 0; r < SCG_MAX_REGIONS; ++r) {
-            st.w[3 * NT + r] = (uint32_t)T.fstart[r];
-            st.w[StrandTable<NT>::STRIDE + 3 * NT + r] = (uint32_t)T.rstart[r];
-            st.w[3 * NT + SCG_MAX_REGIONS + r] = (uint32_t)T.flen[r];
-            st.w[StrandTable<NT>::STRIDE + 3 * NT + SCG_MAX_REGIONS + r] = (uint32_t)T.rlen[r];
-        }
+        st.w[i] = word;
     }
 }
 
@@ -548,12 +664,18 @@ enum class Lane { idle, unstaged, ready };
 // lane.  `unstaged`: the workgroup's span or this lane's read does not fit the tile.  The host picks the tile shape from
 // the batch's maximum read length, so that bound was wrong: the caller flags it (reported by scg_plan_read) instead of
 // guessing.  `ready`: `sr` is the lane's read (lane_read()).
-template<int NW, int NT>
-__device__ __forceinline__ Lane stage_tile(const ScgScan& T, const ScgReads& R, int64_t n_reads, Tile<NW>& tile, StagedRead& sr) {
+// The strand table, and whatever else of the kernel arguments the caller keeps in LDS (`fill_more`), is filled behind
+// the issue of the tile's first loads (stage_reads) and is visible after the barrier, as the tile is.
+template<int NW, int NT, class Fill = NoFill>
+__device__ __forceinline__ Lane stage_tile(const ScgScan& T, const ScgReads& R, int64_t n_reads, Tile<NW>& tile, StrandTable<NT>& strands, StagedRead& sr,
+                                           Fill&& fill_more = Fill()) {
     const int64_t r0 = (int64_t)blockIdx.x * STAGE_BLOCK;
     const int nr = (int)((n_reads - r0) < STAGE_BLOCK ? (n_reads - r0) : STAGE_BLOCK);
     int64_t span0 = 0;
-    const bool staged = (T.len <= 32 * NT) && stage_reads<NW>(R, n_reads, r0, nr, tile, span0);
+    const bool staged = (T.len <= 32 * NT) && stage_reads<NW, true>(R, n_reads, r0, nr, tile, span0, [&]() {
+        fill_strand_table<NT>(strands, T);
+        fill_more();
+    });
     __syncthreads();
     if ((int)threadIdx.x >= nr) return Lane::idle;
     const Read rd = get_read(R, r0 + threadIdx.x);
